@@ -2,7 +2,14 @@
 per GPU, bf16 MFMA compute (BASELINE.json `metric`, configs[1]), plus the logit
 max-abs-error vs the fp32 CPU reference and a roofline line for the dominant kernel.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--no-cpu-baseline]
+A plain run sets up, warms up, times the K steps and prints the headline record (`metric`,
+`value`, `ms_per_step`, ...); everything that takes passes of its own -- the fp16 legs, the
+roofline and per-kernel tables, the CPU baselines and logit errors -- runs only with --full.
+--dump-outputs DIR writes what the last timed step returned (the logits; in train mode the loss
+too) as DIR/<name>.npy; the inputs are seeded, so two builds compare output for output.
+
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dump-outputs DIR]
+  python bench.py --full [--no-cpu-baseline] [...]   # the whole record, every mode
   python bench.py --mode train [...]   # BASELINE configs[4]: ViViT-B train step (fwd + bwd +
                                        # AdamW) bf16, 4 clips per GPU, RCCL gradient all-reduce
   python bench.py --mode timesformer   # BASELINE configs[2]: TimeSformer-B 8f, 16 clips per GPU
@@ -186,6 +193,39 @@ def timed_loop(step, steps: int, warmup: int, dist=None, sync=None):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     return dt
+
+
+DUMP_LIMIT_BYTES = 60 << 20      # --dump-outputs: array bytes in all (under 64 MB with the .npy headers)
+
+
+def dump_outputs(dirname: str, arrays: dict, rank: int = 0, world: int = 1):
+    """--dump-outputs: what the last timed step returned (`arrays`: name -> tensor) as
+    DIR/<name>.npy (rank r of N > 1: <name>_rank<r>.npy), float64 kept, anything else as float32.
+    Beyond DUMP_LIMIT_BYTES in all, each array is cut to an equal share of the limit: a fixed
+    sample of its flattened elements (RandomState(0) indices, sorted), the same from run to run."""
+    os.makedirs(dirname, exist_ok=True)
+    host = {}
+    for name, t in arrays.items():
+        v = t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
+        host[name] = np.ascontiguousarray(v, dtype=np.float64 if v.dtype == np.float64 else np.float32)
+    if sum(v.nbytes for v in host.values()) > DUMP_LIMIT_BYTES:
+        share = DUMP_LIMIT_BYTES // len(host)
+        for name, v in host.items():
+            keep = share // v.itemsize
+            if v.size > keep:
+                idx = np.sort(np.random.RandomState(0).choice(v.size, size=keep, replace=False))
+                host[name] = v.reshape(-1)[idx]
+    for name, v in host.items():
+        np.save(os.path.join(dirname, name + (f"_rank{rank}" if world > 1 else "") + ".npy"), v)
+
+
+def headline_record(a, world: int, metric: str, dt: float, data: str, config: dict, **more):
+    """The record of a plain run (no --full): the headline fields as the full record has them, from the
+    `dt` seconds the a.steps timed steps took."""
+    return dict({"metric": metric, "value": round(a.batch * a.steps * world / dt, 2), "unit": "clips/s",
+                 "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(dt / a.steps * 1e3, 3),
+                 "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "bf16", "data": data,
+                 "config": config}, **more, build=_build_id())
 
 
 PEAK_HBM_GBS = 8000.0            # MI355X HBM3E spec (MI355X_MICROARCH.md)
@@ -460,9 +500,10 @@ def run_family(a, dist, rank, world, dev):
         x = torch.from_numpy(make_synthetic_video(a.batch, 32, 224, seed=1 + rank)).to(dev)
 
     model.graph_replay = bool(a.graph)
+    last = [None]  # what the latest step returned (the model's logits buffer)
 
     def step():
-        model.forward_logits(x)
+        last[0] = model.forward_logits(x)
 
     def timed(streams):
         model.concurrent_streams = streams
@@ -476,6 +517,18 @@ def run_family(a, dist, rank, world, dev):
     # the roofline line (the step's dominant kernel)
     dt = timed(a.streams)
     tune = _stream_tuning(model)
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, {"logits": last[0]}, rank, world)
+    data = "synthetic (uint8 frames RandomState(1+rank) -> the family's processor affine; weights RandomState(0))"
+    if not a.full:
+        out = None
+        if rank == 0:
+            out = headline_record(a, world, metric, dt, data,
+                                  {"workload": workload, "global_batch": a.batch * world, "parallelism": f"dp{world}",
+                                   "streams": a.streams, "hip_graph": _graph_used(model, a),
+                                   "stream_sets_timed": tune})
+            print(json.dumps(out), flush=True)
+        return out
     model.graph_replay = False  # the passes below are event-instrumented or one-off calls
     dt1 = timed(1)
     # the per-kernel table on the headline's own launches: its split, the parts serialised on one stream
@@ -519,8 +572,7 @@ def run_family(a, dist, rank, world, dev):
         out = {
             "metric": metric, "value": round(value, 2), "unit": "clips/s", "n_gpus": world, "steps": a.steps,
             "warmup": a.warmup, "ms_per_step": round(ms_per_step, 3), "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": "bf16",
-            "data": "synthetic (uint8 frames RandomState(1+rank) -> the family's processor affine; weights RandomState(0))",
+            "vs_baseline": None, "dtype": "bf16", "data": data,
             "config": {"workload": workload, "global_batch": a.batch * world, "parallelism": f"dp{world}",
                        "streams": a.streams, "hip_graph": _graph_used(model, a), "stream_sets_timed": tune},
             "logit_max_abs_err": err,
@@ -578,6 +630,7 @@ def run_train(a, dist, rank, world, dev):
     labels = torch.from_numpy(np.random.RandomState(2 + rank).randint(0, 2, size=a.batch)).long().to(dev)
     crit = torch.nn.CrossEntropyLoss()
     losses = []
+    last = {}  # what the latest eager step returned beside its loss
 
     def step():
         opt.zero_grad()
@@ -588,6 +641,7 @@ def run_train(a, dist, rank, world, dev):
             sync.wait()
         opt.step()
         losses.append(loss.detach())
+        last["logits"] = outputs.logits.detach()
 
     # --train-graph 1 at world size 1: the whole step (forward, loss, backward, AdamW) captured once into a
     # hipGraph and replayed (vivit_train.GraphedTrainStep: the same kernels in the same order, bit-identical to
@@ -606,6 +660,22 @@ def run_train(a, dist, rank, world, dev):
             step()
     torch.cuda.synchronize()
     dt = timed_loop(timed_step, a.steps, 1 if graphed else 0, dist, torch.cuda.synchronize)
+    if a.dump_outputs:  # the last timed step's loss (and, from the eager step, its logits)
+        dump_outputs(a.dump_outputs, dict({} if graphed else last, loss=losses[-1]), rank, world)
+    data = ("synthetic (uint8 frames RandomState(1+rank) -> ViViT processor affine, labels RandomState(2+rank); "
+            "weights RandomState(0))")
+    config = {"workload": f"ViViT-B/16x2 train step, 32x224x224 clips, batch {a.batch} per GPU, AdamW(lr 1e-3, "
+                          "wd 0.01), RCCL gradient all-reduce for N > 1 (BASELINE configs[4])",
+              "model": "ViViT-B/16x2 (joint space-time, 12L, d768, 12H, 3137 tokens)",
+              "global_batch": a.batch * world, "seq_len": 3137, "parallelism": f"dp{world}",
+              "hip_graph": graphed}
+    if not a.full:
+        out = None
+        if rank == 0:
+            out = headline_record(a, world, "clips/sec train step (fwd+bwd+AdamW) ViViT-B 32x224^2 bf16", dt, data,
+                                  config, loss_first_last=[round(float(losses[0]), 5), round(float(losses[-1]), 5)])
+            print(json.dumps(out), flush=True)
+        return out
     # the attention backward's roofline: HIP events around each of its launches in 2 extra eager steps (an
     # event inside a replayed graph would be frozen at capture)
     evs = []
@@ -649,14 +719,7 @@ def run_train(a, dist, rank, world, dev):
             "metric": "clips/sec train step (fwd+bwd+AdamW) ViViT-B 32x224^2 bf16",
             "value": round(value, 2), "unit": "clips/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
             "ms_per_step": round(ms_per_step, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "bf16",
-            "data": "synthetic (uint8 frames RandomState(1+rank) -> ViViT processor affine, labels RandomState(2+rank); "
-                    "weights RandomState(0))",
-            "config": {"workload": f"ViViT-B/16x2 train step, 32x224x224 clips, batch {a.batch} per GPU, AdamW(lr 1e-3, "
-                                   "wd 0.01), RCCL gradient all-reduce for N > 1 (BASELINE configs[4])",
-                       "model": "ViViT-B/16x2 (joint space-time, 12L, d768, 12H, 3137 tokens)",
-                       "global_batch": a.batch * world, "seq_len": 3137, "parallelism": f"dp{world}",
-                       "hip_graph": graphed},
+            "dtype": "bf16", "data": data, "config": config,
             "loss_first_last": [round(float(losses[0]), 5), round(float(losses[-1]), 5)],
             "roofline": {"bound": "mfma", "kernel": "attention backward (attn_bwd_dkdv + attn_bwd_dq + prep)",
                          "achieved": round(attn_tflops, 1), "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s",
@@ -684,8 +747,13 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--mode", choices=["fwd", "train", "timesformer", "swin", "resnet3d"], default="fwd")
     ap.add_argument("--batch", type=int, default=None, help="clips per GPU per step (fwd 8, train 4)")
-    ap.add_argument("--cpu-clips", type=int, default=None)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run everything beside the headline: the fp16 legs, the "
+                         "roofline and per-kernel passes, the CPU baselines and the logit errors against them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float32)")
+    ap.add_argument("--cpu-clips", type=int, default=None, help="--full: clips of the CPU baseline's B = 1 sample")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without its CPU legs")
     ap.add_argument("--streams", type=int, default=None,
                     help="inference modes: concurrent HIP streams the batch is split over in the headline pass "
                          "(default 2; swin 4: its late stages' short launches, measured under graph replay)")
@@ -744,9 +812,10 @@ def main():
     pix = torch.from_numpy(make_synthetic_clips(a.batch, 32, 224, seed=1 + rank)).to(dev)
 
     model.graph_replay = bool(a.graph)
+    last = [None]  # what the latest step returned (the model's logits buffer)
 
     def step():
-        model.forward_logits(pix)
+        last[0] = model.forward_logits(pix)
 
     def timed(streams, evs=None):
         """W warm-up + K timed steps with the batch on `streams` concurrent HIP streams; `evs`: a list
@@ -768,6 +837,23 @@ def main():
     split = list(model.last_split)  # clips per part (vivit.SPLIT_DEFAULT: 5 + 3 at B = 8 on two streams)
     split_desc = " + ".join(str(v) for v in split)
     graphed = model.graph_replay
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, {"logits": last[0]}, rank, world)
+    data = "synthetic (uint8 frames RandomState(1+rank) -> ViViT processor affine; weights RandomState(0))"
+    config = {"workload": "ViViT-B/16x2 forward, 32x224x224 clips, batch 8 per GPU (BASELINE configs[1])",
+              "model": "ViViT-B/16x2 (joint space-time, 12L, d768, 12H, 3137 tokens)",
+              "global_batch": a.batch * world, "seq_len": 3137, "parallelism": f"dp{world}",
+              "streams": a.streams, "split": split, "hip_graph": _graph_used(model, a),
+              "stream_sets_timed": tune}
+    if not a.full:
+        out = None
+        if rank == 0:
+            out = headline_record(a, world, "clips/sec fwd ViViT-B 32x224^2 bf16", dt, data, config)
+            print(json.dumps(out), flush=True)
+        if dist:
+            dist.barrier()
+            dist.destroy_process_group()
+        return out
     # the fp16-operand build of the same forward (VC_ELEM_F16: same kernels, same MFMA rate, logits
     # within 1e-3) and its split-operand variant (precise_layers = 1 with PRECISE_OPS: the weights of
     # the first layers set the fp16 build's logit error), each timed like the headline
@@ -863,12 +949,8 @@ def main():
             "scaling": "weak",
             "vs_baseline": None,
             "dtype": "bf16",
-            "data": "synthetic (uint8 frames RandomState(1+rank) -> ViViT processor affine; weights RandomState(0))",
-            "config": {"workload": "ViViT-B/16x2 forward, 32x224x224 clips, batch 8 per GPU (BASELINE configs[1])",
-                       "model": "ViViT-B/16x2 (joint space-time, 12L, d768, 12H, 3137 tokens)",
-                       "global_batch": a.batch * world, "seq_len": 3137, "parallelism": f"dp{world}",
-                       "streams": a.streams, "split": split, "hip_graph": _graph_used(model, a),
-                       "stream_sets_timed": tune},
+            "data": data,
+            "config": config,
             "logit_max_abs_err": logit_err,
             "roofline": {"bound": "mfma", "kernel": ATTN_KERNEL, "achieved": round(attn_tflops, 1),
                          "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s", "frac": round(attn_tflops / PEAK_BF16_TFLOPS, 4),

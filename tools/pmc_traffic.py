@@ -40,7 +40,7 @@ def main():
     ap.add_argument("fetch_dir")
     ap.add_argument("write_dir")
     ap.add_argument("--out", default=None)
-    ap.add_argument("--cmd", default="python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline")
+    ap.add_argument("--cmd", default="python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline")
     a = ap.parse_args()
     fe = per_kernel(a.fetch_dir, "FETCH_SIZE")
     wr = per_kernel(a.write_dir, "WRITE_SIZE")

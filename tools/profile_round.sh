@@ -14,8 +14,8 @@ mkdir -p $OUT
 STEPS=${STEPS:-20}
 BENCH_ARGS=${BENCH_ARGS:-}
 if [ "$MODE" = "train" ]; then
-  PROF="bench.py --mode train --steps 3 --warmup 1 --no-cpu-baseline"
-  TRACE="bench.py --mode train --steps $STEPS --no-cpu-baseline"
+  PROF="bench.py --full --mode train --steps 3 --warmup 1 --no-cpu-baseline"
+  TRACE="bench.py --full --mode train --steps $STEPS --no-cpu-baseline"
 else
   # counters and the per-kernel durations bench.py's roofline is checked against: the headline's own
   # launches serialised on one stream (--serial 1, as bench.py times them); the concurrent headline
@@ -60,7 +60,7 @@ done
 python3 tools/collect_profiles.py $TAG --dst $OUT/prof > /dev/null || exit 1
 if [ -z "$NO_BENCH" ]; then
   echo "== bench"
-  VCLIP_PROFILES=$OUT/prof timeout -k 10 400 python3 bench.py --mode $MODE --steps $STEPS $BENCH_ARGS > $OUT/bench.log 2>&1
+  VCLIP_PROFILES=$OUT/prof timeout -k 10 400 python3 bench.py --full --mode $MODE --steps $STEPS $BENCH_ARGS > $OUT/bench.log 2>&1
   rc=$?; tail -c 400 $OUT/bench.log; echo; [ $rc -eq 0 ] || exit $rc
   grep '^{' $OUT/bench.log | tail -1 > $OUT/bench.json
 fi

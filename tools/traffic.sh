@@ -5,7 +5,7 @@
 set -o pipefail
 mkdir -p gpurun_out/traffic
 cd /tmp && export TMPDIR=/tmp && cd - > /dev/null
-CMD="bench.py --steps 2 --warmup 1 --no-cpu-baseline"
+CMD="bench.py --full --steps 2 --warmup 1 --no-cpu-baseline"
 for c in FETCH_SIZE WRITE_SIZE; do
   timeout -k 10 300 rocprofv3 --pmc $c --output-format csv -d gpurun_out/traffic/$c -o run -- python3 $CMD \
     > gpurun_out/traffic/$c.log 2>&1 || { echo "pmc pass $c failed"; tail -20 gpurun_out/traffic/$c.log; exit 1; }
