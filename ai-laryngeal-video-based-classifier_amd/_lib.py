@@ -120,6 +120,14 @@ SIGNATURES = {
     "vc_temporal_attention_bwd": ([c_p, c_i64, c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_p, c_i64, c_p], c_int),
     "vc_gelu_erf": ([c_p, c_i64, c_i64, c_i64, c_p, c_i64, c_p], c_int),
     "vc_gelu_erf_bwd": ([c_p, c_int, c_i64, c_p, c_i64, c_i64, c_i64, c_p, c_i64, c_p], c_int),
+    # ResNet50-LSTM (csrc/lstm.hip)
+    "vc_frame_avgpool": ([c_p, c_int, c_i64, c_i64, c_i64, c_i64, c_p, c_i64, c_p], c_int),
+    "vc_bn_apply_h16": ([c_p, c_i64, c_i64, c_i64, c_p, c_p, c_p, c_p, c_i64, c_int, c_p, c_i64, c_p], c_int),
+    "vc_video_to_cl_h16": ([c_p, c_i64, c_i64, c_i64, c_p, c_p], c_int),
+    "vc_lstm_seq_fwd": ([c_p, c_i64, c_i64, c_i64, c_i64, c_p, c_p, c_p, c_i64, c_p, c_p, c_p, c_p, c_i64, c_p], c_int),
+    "vc_lstm_seq_bwd": ([c_p, c_p, c_i64, c_i64, c_i64, c_p, c_p, c_i64, c_int, c_p, c_p, c_p, c_i64, c_p], c_int),
+    "vc_mlp_head_fwd": ([c_p, c_i64, c_i64, c_p, c_p, c_i64, c_p, c_p, c_p, c_i64, c_p, c_p, c_p], c_int),
+    "vc_mlp_head_bwd": ([c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_p, c_p, c_p, c_p, c_p, c_p], c_int),
 }
 
 

@@ -19,7 +19,12 @@ Every arithmetic op here is a HIP kernel of libvclip.so, forward and backward:
   im2col_cl / batchnorm / maxpool / resnet_head   the ResNet3D train step (conv3d_bwd.hip):
               vc_conv3d_im2col / vc_col2im_cl, BatchNorm3d with batch statistics (+ residual, ReLU)
               vc_batchnorm_train_fwd / _bwd, vc_maxpool3d / vc_maxpool3d_bwd, the head with its
-              dropout vc_resnet_head_train / vc_pool_head_bwd / vc_resnet_head_train_bwd.
+              dropout vc_resnet_head_train / vc_pool_head_bwd / vc_resnet_head_train_bwd;
+  lstm_layer  one nn.LSTM layer over all T steps (lstm.hip): the input projection as one bf16 MFMA GEMM
+              with b_ih + b_hh fused, the fp32 recurrence vc_lstm_seq_fwd (train variant: gates, c and
+              bf16 h_prev saved; optional inter-layer dropout mask on the stored h_seq), backward
+              vc_lstm_seq_bwd (BPTT) + vc_wgrad_bf16 (dW_ih, dW_hh) + vc_colsum (db) + the dgrad GEMM (dx);
+  mlp_head    Linear -> ReLU -> Dropout -> Linear in fp32, vc_mlp_head_fwd / vc_mlp_head_bwd.
 The tensors between them (residual adds, the clip <-> frame permutes, the CLS frame mean) are
 ordinary torch tensor ops: layout glue, autograd's bookkeeping.  Rows are padded internally to the
 kernels' tile multiples; the returned tensors have exactly the caller's rows.
@@ -509,3 +514,135 @@ def resnet_head(x, wc, bc, keep, B, T, HW, pool_t):
     per (clip, pooled position, channel)."""
     return _ResnetHead.apply(x, wc, bc, keep, B, T, HW, pool_t)
 
+
+
+def pack_lstm_weights(w_ih: torch.Tensor, w_hh: torch.Tensor) -> dict:
+    """The operand images of one LSTM layer's weights: W_ih as bf16 [Np, Kp] and its transpose
+    [Kp, Np] (padded to the GEMM tiles with zeros), W_hh transposed to f32 [H, 4H] (the forward
+    recurrence reads it coalesced) and contiguous [4H, H] (the backward).  Callers that keep it must
+    remake it when the masters change (VideoResNet50LSTM keys it like ResNet3d._weights_version)."""
+    N, K = w_ih.shape
+    Np, Kp = _round_up(N, 128), _round_up(K, 128)
+    wc = w_ih.detach().float()
+    if (Np, Kp) != (N, K):
+        wc = torch.zeros(Np, Kp, dtype=torch.float32, device=w_ih.device)
+        wc[:N, :K].copy_(w_ih.detach())
+    wb = torch.empty(Np, Kp, dtype=torch.bfloat16, device=w_ih.device)
+    wt = torch.empty(Kp, Np, dtype=torch.bfloat16, device=w_ih.device)
+    ops.pack_weight(wc.contiguous(), wb, wt)
+    whh = w_hh.detach().float().contiguous()
+    return dict(wb=wb, wt=wt, w_hh=whh, w_hh_t=whh.t().contiguous())
+
+
+class _LstmLayer(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, w_ih, w_hh, b_ih, b_hh, B: int, T: int, keep, last_only: bool, need_dx: bool, packed):
+        M, Din = x.shape
+        if M != B * T:
+            raise _lib.VclipError(f"lstm_layer: x has {M} rows, B*T = {B * T}")
+        H = w_hh.shape[1]
+        if tuple(w_hh.shape) != (4 * H, H) or tuple(w_ih.shape) != (4 * H, Din):
+            raise _lib.VclipError("lstm_layer: w_ih [4H, Din], w_hh [4H, H]")
+        pk = packed if packed is not None else pack_lstm_weights(w_ih, w_hh)
+        Np, Kp = pk["wb"].shape
+        Mp, Hp = _round_up(M, 256), _round_up(H, 128)
+        dev = x.device
+        xp = _as_operand(x.detach(), Mp, Kp)
+        bb = torch.zeros(Np, dtype=torch.float32, device=dev)
+        bb[: 4 * H] = b_ih.detach().float() + b_hh.detach().float()
+        pre = torch.empty(Mp, Np, dtype=torch.float32, device=dev)
+        ops.gemm(xp, pk["wb"], bb, "bias_f32", pre, op="lstm_ih")
+        h_seq = torch.zeros(Mp, Hp, dtype=torch.bfloat16, device=dev)
+        h_prev = torch.zeros(Mp, Hp, dtype=torch.bfloat16, device=dev)
+        h_last = torch.empty(B, H, dtype=torch.float32, device=dev)
+        gates = torch.empty(M, 4 * H, dtype=torch.float32, device=dev)
+        c_seq = torch.empty(M, H, dtype=torch.float32, device=dev)
+        kp = None if keep is None else keep.detach().float().contiguous().view(M, H)
+        ops.lstm_seq_fwd(pre, B, T, H, pk["w_hh_t"], h_seq, h_last, keep=kp, gates=gates, c_seq=c_seq, h_prev=h_prev)
+        ctx.save_for_backward(xp, h_prev, gates, c_seq, pk["wt"], pk["w_hh"], *([kp] if kp is not None else []))
+        ctx.dims = (B, T, H, Din, last_only, need_dx, x.dtype)
+        ctx.set_materialize_grads(False)
+        out = h_seq[:M, :H]
+        if last_only:
+            ctx.mark_non_differentiable(out)
+        return out, h_last
+
+    @staticmethod
+    def backward(ctx, dh_seq, dh_last):
+        xp, h_prev, gates, c_seq, wt, w_hh = ctx.saved_tensors[:6]
+        kp = ctx.saved_tensors[6] if len(ctx.saved_tensors) > 6 else None
+        B, T, H, Din, last_only, need_dx, xdtype = ctx.dims
+        M = B * T
+        Mp, Kp = xp.shape
+        Np, Hp = wt.shape[1], h_prev.shape[1]
+        dev = xp.device
+        if last_only:
+            dh = (dh_last if dh_last is not None else torch.zeros(B, H, device=dev)).float().contiguous()
+        else:
+            dh = (dh_seq.float() if dh_seq is not None else torch.zeros(M, H, device=dev)).contiguous()
+            if dh_last is not None:
+                # h_last is the unmasked h_{T-1}, but the kernel masks every incoming row
+                if kp is not None:
+                    raise _lib.VclipError("lstm_layer: with a keep mask, gradients through both h_seq and h_last are "
+                                          "not supported (use last_only=True when only h_last is used)")
+                dh = dh.clone() if dh is dh_seq else dh
+                dh.view(B, T, H)[:, T - 1] += dh_last.float()
+        dpre = torch.empty(M, 4 * H, dtype=torch.float32, device=dev)
+        dpb = torch.zeros(Mp, Np, dtype=torch.bfloat16, device=dev)
+        # last_only: dh is dL/dh_last, the gradient of the UNMASKED h_{T-1} (the mask only scaled the stored,
+        # here non-differentiable, h_seq), so the kernel must not mask it
+        ops.lstm_seq_bwd(gates, c_seq, B, T, H, w_hh, dh, dpre, dpb, last_only=last_only,
+                         keep=None if last_only else kp)
+        dw_ih = torch.empty(Np, Kp, dtype=torch.float32, device=dev)
+        ops.wgrad(dpb, xp, dw_ih, ops.wgrad_work(Mp, Np, Kp, dev))
+        dw_hh = torch.empty(Np, Hp, dtype=torch.float32, device=dev)
+        ops.wgrad(dpb, h_prev, dw_hh, ops.wgrad_work(Mp, Np, Hp, dev))
+        db = torch.empty(4 * H, dtype=torch.float32, device=dev)
+        ops.colsum(dpre, db, ops.colsum_work(M, 4 * H, dev), m=M)
+        dx = None
+        if need_dx:
+            dxp = torch.empty(Mp, Kp, dtype=torch.float32, device=dev)
+            ops.gemm(dpb, wt, _zeros_f32(Kp, dev), "bias_f32", dxp, op="lstm_dx")
+            dx = dxp[:M, :Din].to(xdtype)
+        return dx, dw_ih[: 4 * H, :Din], dw_hh[: 4 * H, :H], db, db.clone(), None, None, None, None, None, None
+
+
+def lstm_layer(x, w_ih, w_hh, b_ih, b_hh, B, T, keep=None, last_only=False, need_dx=True, packed=None):
+    """One nn.LSTM layer (batch_first, zero initial state) over x bf16 [B*T, Din] (row b*T + t) with the
+    fp32 masters w_ih [4H, Din], w_hh [4H, H], b_ih, b_hh [4H] -> (h_seq bf16 [B*T, H], h_last f32 [B, H]).
+    keep f32 [B*T, H] (0 or 1 / (1 - p)) is nn.LSTM's inter-layer dropout: it scales h_seq only; h_last
+    is the unmasked h_{T-1} and its gradient is never masked.
+    last_only: only h_last carries gradient (the top layer; h_seq is then not differentiable).
+    With a keep mask, gradients through BOTH h_seq and h_last in one backward are refused.
+    need_dx=False skips the input gradient (layer 0 behind a frozen backbone).  The input gradient
+    has x's dtype.  packed: pack_lstm_weights(w_ih, w_hh) kept by the caller.  hidden % 4 == 0, <= 1024."""
+    return _LstmLayer.apply(x, w_ih, w_hh, b_ih, b_hh, B, T, keep, last_only, need_dx, packed)
+
+
+class _MlpHead(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, h, w1, b1, w2, b2, keep):
+        hc = h.detach().float().contiguous()
+        w1c, b1c, w2c, b2c = (t.detach().float().contiguous() for t in (w1, b1, w2, b2))
+        B, H1, nl = hc.shape[0], w1c.shape[0], w2c.shape[0]
+        kp = None if keep is None else keep.detach().float().contiguous()
+        hid = torch.empty(B, H1, dtype=torch.float32, device=hc.device)
+        logits = torch.empty(B, nl, dtype=torch.float32, device=hc.device)
+        ops.mlp_head_fwd(hc, w1c, b1c, w2c, b2c, logits, keep=kp, hid=hid)
+        ctx.save_for_backward(hc, w1c, w2c, hid, *([kp] if kp is not None else []))
+        return logits
+
+    @staticmethod
+    def backward(ctx, dlogits):
+        h, w1, w2, hid = ctx.saved_tensors[:4]
+        kp = ctx.saved_tensors[4] if len(ctx.saved_tensors) > 4 else None
+        e = lambda *s: torch.empty(*s, dtype=torch.float32, device=h.device)  # noqa: E731
+        dh, dw1, db1, dw2, db2 = e(*h.shape), e(*w1.shape), e(w1.shape[0]), e(*w2.shape), e(w2.shape[0])
+        ops.mlp_head_bwd(h, w1, w2, hid, kp, dlogits.float().contiguous(), dh, dw1, db1, dw2, db2)
+        return dh, dw1, db1, dw2, db2, None
+
+
+def mlp_head(h, w1, b1, w2, b2, keep=None):
+    """The ResNet50-LSTM classifier Linear(H, H1) -> ReLU -> Dropout -> Linear(H1, labels) on f32 h [B, H];
+    keep f32 [B, H1] = the dropout scale (0 or 1 / (1 - p)), None = no dropout."""
+    return _MlpHead.apply(h, w1, b1, w2, b2, keep)

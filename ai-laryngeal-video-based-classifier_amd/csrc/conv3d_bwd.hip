@@ -385,8 +385,8 @@ int vc_batchnorm_train_fwd(const float* y, int64_t ldy, int64_t M, int64_t C, co
                            float eps, float momentum, float* running_mean, float* running_var, const void* res,
                            int res_bf16, int64_t ldr, int relu, uint16_t* z, int64_t ldz, float* stat, float* work,
                            int64_t work_elems, hipStream_t stream) {
-    if (!y || !gamma || !beta || !z || !stat || !work) return fail(VC_ERR_INVALID_ARG, "vc_batchnorm_train_fwd: null pointer");
-    if (M <= 0 || C <= 0 || C % 4 || ldy % 4 || ldy < C || ldz < C || ((uintptr_t)y & 15))
+    if (!y || !gamma || !beta || !stat || !work) return fail(VC_ERR_INVALID_ARG, "vc_batchnorm_train_fwd: null pointer");
+    if (M <= 0 || C <= 0 || C % 4 || ldy % 4 || ldy < C || (z && ldz < C) || ((uintptr_t)y & 15))
         return fail(VC_ERR_INVALID_ARG, "vc_batchnorm_train_fwd: bad shape (C % 4, 16-B rows)");
     if ((running_mean == nullptr) != (running_var == nullptr))
         return fail(VC_ERR_INVALID_ARG, "vc_batchnorm_train_fwd: running_mean and running_var go together");
@@ -400,6 +400,7 @@ int vc_batchnorm_train_fwd(const float* y, int64_t ldy, int64_t M, int64_t C, co
     bn_partial_kernel<1><<<gp, 256, 0, stream>>>(y, ldy, M, (int)C, rps, stat, nullptr, 0, nullptr, 0, 0, work);
     bn_finalize_kernel<1><<<gf, 256, 0, stream>>>(work, (int)ns, M, (int)C, eps, momentum, stat, running_mean,
                                                   running_var, nullptr, nullptr);
+    if (!z) return check_launch("vc_batchnorm_train_fwd");  // statistics only
     const unsigned ga = (unsigned)((M * (C / 4) + 255) / 256);
     if (res && res_bf16)
         bn_apply_kernel<uint16_t><<<ga, 256, 0, stream>>>(y, ldy, M, (int)C, stat, gamma, beta, (const uint16_t*)res, ldr,

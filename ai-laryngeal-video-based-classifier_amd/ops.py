@@ -952,3 +952,192 @@ def pack_weight(src: torch.Tensor, dst: torch.Tensor | None = None, dst_t: torch
         _need(dst_t.dtype == torch.bfloat16 and dst_t.is_contiguous() and tuple(dst_t.shape) == (K, N), "pack_weight dst_t")
     _lib.call("vc_pack_weight", _p(src), N, K, nscaled, scale, _p(dst) if dst is not None else None,
               _p(dst_t) if dst_t is not None else None, _stream(src))
+
+
+# ---- ResNet50-LSTM (csrc/lstm.hip) ------------------------------------------------------------
+def lstm_group(hidden: int) -> int:
+    """Sequences one workgroup of the recurrence kernels owns (csrc/lstm.hip group_of)."""
+    return 4 if hidden <= 512 else 2
+
+
+def _lstm_shape(B: int, T: int, hidden: int):
+    _need(B >= 1 and T >= 1, "lstm: B and T must be >= 1")
+    _need(0 < hidden <= 1024 and hidden % 4 == 0,
+          f"lstm: unsupported hidden size {hidden} (hidden % 4 == 0 and hidden <= 1024)")
+
+
+def frame_avgpool(x: torch.Tensor, N: int, P: int, C: int, out: torch.Tensor) -> torch.Tensor:
+    """out[n] = mean of rows n*P .. n*P + P - 1 of x (channels-last bf16 or fp16, fp32 sum) -> bf16 [N, C]."""
+    _dev(x, out)
+    _need(N >= 1 and P >= 1 and C >= 1, "frame_avgpool: empty shape")
+    _need(x.dtype in H16 and out.dtype == torch.bfloat16 and x.dim() == 2 and out.dim() == 2 and
+          x.shape[0] >= N * P and x.shape[1] >= C and out.shape[0] >= N and out.shape[1] >= C and x.stride(1) == 1 and
+          out.stride(1) == 1, "frame_avgpool: x bf16 / fp16 [>= N*P, >= C], out bf16 [>= N, >= C]")
+    timed("frame_avgpool_kernel", "avgpool", (N * P + N) * C * 2, "byte", _lib.call, "vc_frame_avgpool", _p(x),
+          ELEM_F16 if x.dtype == torch.float16 else 0, x.stride(0), N, P, C, _p(out), out.stride(0), _stream(x))
+    return out
+
+
+def batchnorm_train_stats(y: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, running_mean: torch.Tensor,
+                          running_var: torch.Tensor, stat: torch.Tensor, eps: float = 1e-5,
+                          momentum: float = 0.1) -> torch.Tensor:
+    """The statistics pass of vc_batchnorm_train_fwd alone: stat f32 [2, C] = [batch mean | rstd] of the f32
+    rows y [M, C] (C % 4 == 0), running_mean / running_var updated in place with `momentum`; no rows written."""
+    _dev(y, gamma, beta, running_mean, running_var, stat)
+    M, C = y.shape
+    _need(y.dtype == torch.float32 and y.stride(1) == 1 and C % 4 == 0 and y.stride(0) % 4 == 0 and
+          y.data_ptr() % 16 == 0, "batchnorm_train_stats: y f32 [M, C], C % 4 == 0, 16-byte rows")
+    for t in (gamma, beta, running_mean, running_var):
+        _need(t.dtype == torch.float32 and t.is_contiguous() and t.numel() == C, "batchnorm_train_stats: f32 [C] vectors")
+    _need(stat.dtype == torch.float32 and stat.is_contiguous() and stat.numel() == 2 * C, "batchnorm_train_stats: stat f32 [2, C]")
+    splits = min(4096, max(1, (M + 127) // 128))  # conv3d_bwd.hip bn_splits
+    work = torch.empty(splits * 2 * C, dtype=torch.float32, device=y.device)
+    _lib.call("vc_batchnorm_train_fwd", _p(y), y.stride(0), M, C, _p(gamma), _p(beta), eps, momentum, _p(running_mean),
+              _p(running_var), None, 1, 0, 0, None, 0, _p(stat), _p(work), work.numel(), _stream(y))
+    return stat
+
+
+def bn_apply_h16(y: torch.Tensor, stat: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, z: torch.Tensor,
+                 res: torch.Tensor | None = None, relu: bool = False) -> torch.Tensor:
+    """z fp16 [M, C] = relu?(gamma (y - mean) rstd + beta (+ res fp16)) for f32 y [M, C] and stat = [mean | rstd]
+    f32 [2, C] of vc_batchnorm_train_fwd."""
+    _dev(y, stat, gamma, beta, z)
+    M, C = y.shape
+    _need(y.dtype == torch.float32 and y.stride(1) == 1 and C % 4 == 0 and y.stride(0) % 4 == 0, "bn_apply_h16 y")
+    _need(stat.dtype == torch.float32 and stat.is_contiguous() and stat.numel() == 2 * C and gamma.numel() == C and
+          beta.numel() == C and gamma.dtype == torch.float32 and beta.dtype == torch.float32 and gamma.is_contiguous() and
+          beta.is_contiguous(), "bn_apply_h16 stat / gamma / beta f32 [C]")
+    _need(z.dtype == torch.float16 and z.stride(1) == 1 and z.shape[0] >= M and z.shape[1] >= C and z.stride(0) % 4 == 0,
+          "bn_apply_h16 z fp16 [>= M, >= C]")
+    if res is not None:
+        _dev(res)
+        _need(res.dtype == torch.float16 and res.stride(1) == 1 and res.shape[0] >= M and res.shape[1] >= C,
+              "bn_apply_h16 res fp16 [>= M, >= C]")
+    _lib.call("vc_bn_apply_h16", _p(y), y.stride(0), M, C, _p(stat), _p(gamma), _p(beta),
+              _p(res) if res is not None else None, res.stride(0) if res is not None else 0, int(relu), _p(z), z.stride(0),
+              _stream(y))
+    return z
+
+
+def video_to_cl_h16(video: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
+    """f32 clip [B, C <= 8, T, H, W] -> channels-last fp16 rows out [B*T*H*W, 8] (channels >= C zero)."""
+    _dev(video, out)
+    _need(video.dtype == torch.float32 and video.is_contiguous() and video.dim() == 5 and 1 <= video.shape[1] <= 8,
+          "video_to_cl_h16: video f32 contiguous [B, C <= 8, T, H, W]")
+    B, C = video.shape[:2]
+    P = video.shape[2] * video.shape[3] * video.shape[4]
+    _need(out.dtype == torch.float16 and out.is_contiguous() and tuple(out.shape) == (B * P, 8), "video_to_cl_h16 out")
+    _lib.call("vc_video_to_cl_h16", _p(video), B, C, P, _p(out), _stream(video))
+    return out
+
+
+def lstm_seq_fwd(pre: torch.Tensor, B: int, T: int, hidden: int, w_hh_t: torch.Tensor, h_seq: torch.Tensor,
+                 h_last: torch.Tensor, keep: torch.Tensor | None = None, gates: torch.Tensor | None = None,
+                 c_seq: torch.Tensor | None = None, h_prev: torch.Tensor | None = None) -> torch.Tensor:
+    """All T steps of one LSTM layer: pre f32 [B*T, 4H] (x W_ih^T + b_ih + b_hh), w_hh_t f32 [H, 4H] =
+    weight_hh transposed -> h_seq bf16 [B*T, H] (times keep f32 [B*T, H] when given), h_last f32 [B, H];
+    with gates / c_seq / h_prev (the train variant) the saved state of vc_lstm_seq_bwd."""
+    _lstm_shape(B, T, hidden)
+    M = B * T
+    _dev(pre, w_hh_t, h_seq, h_last)
+    _need(pre.dtype == torch.float32 and pre.dim() == 2 and pre.shape[0] >= M and pre.shape[1] >= 4 * hidden and
+          pre.stride(1) == 1, "lstm_seq_fwd: pre f32 [>= B*T, >= 4H]")
+    _need(w_hh_t.dtype == torch.float32 and w_hh_t.is_contiguous() and tuple(w_hh_t.shape) == (hidden, 4 * hidden),
+          "lstm_seq_fwd: w_hh_t f32 contiguous [H, 4H] (weight_hh transposed)")
+    _need(h_seq.dtype == torch.bfloat16 and h_seq.dim() == 2 and h_seq.shape[0] >= M and h_seq.shape[1] >= hidden and
+          h_seq.stride(1) == 1, "lstm_seq_fwd: h_seq bf16 [>= B*T, >= H]")
+    _need(h_last.dtype == torch.float32 and h_last.is_contiguous() and h_last.numel() >= B * hidden,
+          "lstm_seq_fwd: h_last f32 [B, H]")
+    if keep is not None:
+        _dev(keep)
+        _need(keep.dtype == torch.float32 and keep.is_contiguous() and keep.numel() >= M * hidden and
+              keep.shape[-1] == hidden, "lstm_seq_fwd: keep f32 contiguous [B*T, H]")
+    train = gates is not None
+    if train:
+        _need(c_seq is not None and h_prev is not None, "lstm_seq_fwd: the train variant needs gates, c_seq and h_prev")
+        _dev(gates, c_seq, h_prev)
+        _need(gates.dtype == torch.float32 and gates.is_contiguous() and gates.shape[-1] == 4 * hidden and
+              gates.numel() >= M * 4 * hidden, "lstm_seq_fwd: gates f32 contiguous [B*T, 4H]")
+        _need(c_seq.dtype == torch.float32 and c_seq.is_contiguous() and c_seq.shape[-1] == hidden and
+              c_seq.numel() >= M * hidden, "lstm_seq_fwd: c_seq f32 contiguous [B*T, H]")
+        _need(h_prev.dtype == torch.bfloat16 and h_prev.dim() == 2 and h_prev.shape[0] >= M and
+              h_prev.shape[1] >= hidden and h_prev.stride(1) == 1, "lstm_seq_fwd: h_prev bf16 [>= B*T, >= H]")
+    ngroups = -(-B // lstm_group(hidden))
+    timed("lstm_seq_fwd_kernel", "lstm_fwd", 4.0 * hidden * hidden * 4 * T * ngroups, "byte", _lib.call,
+          "vc_lstm_seq_fwd", _p(pre), pre.stride(0), B, T, hidden, _p(w_hh_t), _p(keep) if keep is not None else None,
+          _p(h_seq), h_seq.stride(0), _p(h_last), _p(gates) if train else None, _p(c_seq) if train else None,
+          _p(h_prev) if train else None, h_prev.stride(0) if train else 0, _stream(pre))
+    return h_last
+
+
+def lstm_seq_bwd(gates: torch.Tensor, c_seq: torch.Tensor, B: int, T: int, hidden: int, w_hh: torch.Tensor,
+                 dh: torch.Tensor, dpre: torch.Tensor, dpre_bf16: torch.Tensor, last_only: bool = False,
+                 keep: torch.Tensor | None = None) -> torch.Tensor:
+    """BPTT of one LSTM layer from the saved gates / c_seq: dh f32 [B*T, H] (dL/dh_seq) or, with
+    last_only, f32 [B, H] (dL/dh_last); w_hh f32 [4H, H] -> dpre f32 [B*T, 4H] and its bf16 copy."""
+    _lstm_shape(B, T, hidden)
+    M = B * T
+    _dev(gates, c_seq, w_hh, dh, dpre, dpre_bf16)
+    _need(gates.dtype == torch.float32 and gates.is_contiguous() and gates.shape[-1] == 4 * hidden and
+          gates.numel() >= M * 4 * hidden, "lstm_seq_bwd: gates f32 contiguous [B*T, 4H]")
+    _need(c_seq.dtype == torch.float32 and c_seq.is_contiguous() and c_seq.shape[-1] == hidden and
+          c_seq.numel() >= M * hidden, "lstm_seq_bwd: c_seq f32 contiguous [B*T, H]")
+    _need(w_hh.dtype == torch.float32 and w_hh.is_contiguous() and tuple(w_hh.shape) == (4 * hidden, hidden),
+          "lstm_seq_bwd: w_hh f32 contiguous [4H, H]")
+    _need(dh.dtype == torch.float32 and dh.dim() == 2 and dh.stride(1) == 1 and dh.shape[1] >= hidden and
+          dh.shape[0] >= (B if last_only else M), "lstm_seq_bwd: dh f32 [B*T, H] ([B, H] with last_only)")
+    _need(dpre.dtype == torch.float32 and dpre.is_contiguous() and dpre.shape[-1] == 4 * hidden and
+          dpre.numel() >= M * 4 * hidden, "lstm_seq_bwd: dpre f32 contiguous [B*T, 4H]")
+    _need(dpre_bf16.dtype == torch.bfloat16 and dpre_bf16.dim() == 2 and dpre_bf16.stride(1) == 1 and
+          dpre_bf16.shape[0] >= M and dpre_bf16.shape[1] >= 4 * hidden, "lstm_seq_bwd: dpre_bf16 bf16 [>= B*T, >= 4H]")
+    if keep is not None:
+        _dev(keep)
+        _need(keep.dtype == torch.float32 and keep.is_contiguous() and keep.numel() >= M * hidden and
+              keep.shape[-1] == hidden, "lstm_seq_bwd: keep f32 contiguous [B*T, H]")
+    ngroups = -(-B // lstm_group(hidden))
+    timed("lstm_seq_bwd_kernel", "lstm_bwd", 4.0 * hidden * hidden * 4 * T * ngroups, "byte", _lib.call,
+          "vc_lstm_seq_bwd", _p(gates), _p(c_seq), B, T, hidden, _p(w_hh), _p(dh), dh.stride(0), int(last_only),
+          _p(keep) if keep is not None else None, _p(dpre), _p(dpre_bf16), dpre_bf16.stride(0), _stream(gates))
+    return dpre
+
+
+def _f32c(name, *ts):
+    for t in ts:
+        _need(t.dtype == torch.float32 and t.is_contiguous(), f"{name}: f32 contiguous tensors")
+
+
+def mlp_head_fwd(h: torch.Tensor, w1, b1, w2, b2, logits: torch.Tensor, keep: torch.Tensor | None = None,
+                 hid: torch.Tensor | None = None) -> torch.Tensor:
+    """logits[B, nl] = W2 (relu(W1 h + b1) * keep) + b2 on f32 h [B, H]; hid f32 [B, H1] (optional) is
+    the masked hidden row the backward needs."""
+    opt = [t for t in (keep, hid) if t is not None]
+    _dev(h, w1, b1, w2, b2, logits, *opt)
+    _f32c("mlp_head_fwd", h, w1, b1, w2, b2, logits, *opt)
+    B, H = h.shape
+    H1, nl = w1.shape[0], w2.shape[0]
+    _need(B >= 1 and 0 < H <= 1024 and 0 < H1 <= 1024 and 0 < nl <= 1024, "mlp_head_fwd: B >= 1; H, H1, labels <= 1024")
+    _need(tuple(w1.shape) == (H1, H) and b1.numel() == H1 and tuple(w2.shape) == (nl, H1) and b2.numel() == nl and
+          tuple(logits.shape) == (B, nl), "mlp_head_fwd shapes")
+    _need(all(tuple(t.shape) == (B, H1) for t in opt), "mlp_head_fwd: keep / hid f32 [B, H1]")
+    timed("mlp_head_fwd_kernel", "head", (B * H + H1 * H) * 4, "byte", _lib.call, "vc_mlp_head_fwd", _p(h), B, H, _p(w1),
+          _p(b1), H1, _p(keep) if keep is not None else None, _p(w2), _p(b2), nl, _p(hid) if hid is not None else None,
+          _p(logits), _stream(h))
+    return logits
+
+
+def mlp_head_bwd(h, w1, w2, hid, keep, dlogits, dh, dw1, db1, dw2, db2):
+    """Backward of mlp_head_fwd from dlogits f32 [B, nl] and the saved hid (keep may be None)."""
+    opt = [keep] if keep is not None else []
+    _dev(h, w1, w2, hid, dlogits, dh, dw1, db1, dw2, db2, *opt)
+    _f32c("mlp_head_bwd", h, w1, w2, hid, dlogits, dh, dw1, db1, dw2, db2, *opt)
+    B, H = h.shape
+    H1, nl = w1.shape[0], w2.shape[0]
+    _need(B >= 1 and 0 < H <= 1024 and 0 < H1 <= 1024 and 0 < nl <= 1024, "mlp_head_bwd: B >= 1; H, H1, labels <= 1024")
+    _need(tuple(w1.shape) == (H1, H) and tuple(w2.shape) == (nl, H1) and tuple(hid.shape) == (B, H1) and
+          tuple(dlogits.shape) == (B, nl) and tuple(dh.shape) == (B, H) and tuple(dw1.shape) == (H1, H) and
+          db1.numel() == H1 and tuple(dw2.shape) == (nl, H1) and db2.numel() == nl and
+          all(tuple(t.shape) == (B, H1) for t in opt), "mlp_head_bwd shapes")
+    timed("mlp_head_bwd_kernel", "head_bwd", (2 * B * H + 2 * H1 * H) * 4, "byte", _lib.call, "vc_mlp_head_bwd", _p(h),
+          _p(w1), _p(w2), _p(hid), _p(keep) if keep is not None else None, _p(dlogits), B, H, H1, nl, _p(dh), _p(dw1),
+          _p(db1), _p(dw2), _p(db2), _stream(h))
+    return dh

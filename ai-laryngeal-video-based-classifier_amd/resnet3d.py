@@ -246,6 +246,24 @@ class ResNet3d(torch.nn.Module):
         average); channels-last rows throughout."""
         from . import autograd_ops as A
         c = self.cfg
+        x, B, (Tf, Hf, Wf), cin = self._forward_train_features(video)
+        pt, ph, pw = c["head_pool"]
+        if (ph, pw) != (Hf, Wf):
+            raise NotImplementedError("train step head: the pool window must cover the final spatial map")
+        npos = Tf - pt + 1
+        keep = torch.ones(B, npos, cin, device=video.device)
+        if self.head_dropout:
+            keep = keep.bernoulli_(0.5).mul_(2.0)  # nn.Dropout(0.5): keep with prob 0.5, scale 1 / 0.5
+        self._packed = None  # the running statistics were updated in place: re-fold before the next eval
+        P = self.P
+        return A.resnet_head(x, P("blocks.5.proj.weight"), P("blocks.5.proj.bias"), keep, B, Tf, Hf * Wf, pt)
+
+    def _forward_train_features(self, video: torch.Tensor):
+        """The train-mode stem and the four stages of _forward_train (batch-statistic BatchNorm, running
+        statistics updated in place); returns (last activations bf16 [B*T*H*W, C], B, (T, H, W), C).
+        The caller drops `_packed` (the folded inference weights) after it."""
+        from . import autograd_ops as A
+        c = self.cfg
         B, Cin, T, H, W = video.shape
         if Cin != 3:
             raise ValueError("video must be [B, 3, T, H, W]")
@@ -297,16 +315,7 @@ class ResNet3d(torch.nn.Module):
                        p + "branch2.norm_c", True, res=sc)
                 cin = P(p + "branch2.conv_c.weight").shape[0]
             g_in = g
-        Tf, Hf, Wf = grids[-1]
-        pt, ph, pw = c["head_pool"]
-        if (ph, pw) != (Hf, Wf):
-            raise NotImplementedError("train step head: the pool window must cover the final spatial map")
-        npos = Tf - pt + 1
-        keep = torch.ones(B, npos, cin, device=video.device)
-        if self.head_dropout:
-            keep = keep.bernoulli_(0.5).mul_(2.0)  # nn.Dropout(0.5): keep with prob 0.5, scale 1 / 0.5
-        self._packed = None  # the running statistics were updated in place: re-fold before the next eval
-        return A.resnet_head(x, P("blocks.5.proj.weight"), P("blocks.5.proj.bias"), keep, B, Tf, Hf * Wf, pt)
+        return x, B, grids[-1], cin
 
     def forward_logits(self, video: torch.Tensor) -> torch.Tensor:
         """logits f32 [B, classes] (a workspace buffer, overwritten by the next call); with

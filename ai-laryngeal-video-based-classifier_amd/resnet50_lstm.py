@@ -1,0 +1,321 @@
+"""ResNet50-LSTM video classifier on the libvclip.so kernels — drop-in for
+`VideoResNet50LSTM(hidden_size=256, num_layers=2, dropout=0.5)` of
+resnet50-2d-lstm/src/models/model.py:5-60, called as `model(f32[B, 3, T, H, W])` -> `f32[B, 1]`,
+in eval mode and in the reference's train loop (resnet50-2d-lstm/src/trainer/trainer.py:156-170).
+
+Per frame, torchvision's ResNet-50 (v1.5, fc removed) runs on the shared conv path
+(resnet3d.ResNet3d with kt = 1 kernels, channels-last bf16); vc_frame_avgpool gives the
+[B*T, 2048] bf16 features.  Each LSTM layer is one MFMA GEMM for the input projections of all T
+steps (bias = b_ih + b_hh, fp32 out) followed by the fp32 recurrence kernel (vc_lstm_seq_fwd);
+the last step's h goes through the hidden -> 64 -> 1 head (vc_mlp_head_fwd).
+
+Training: the backbone is frozen (model.py:15-16: requires_grad = False; trainer.py:45-48 hands
+Adam the trainable parameters only), but `model.train()` still puts its BatchNorm layers into
+training mode, so the reference normalises with batch statistics and updates the running
+statistics.  That is what train mode does here too: a no-grad forward of the backbone with fp32
+batch statistics and fp16 activation rows (`_train_features_h16`; ResNet3d's own train-mode forward,
+which keeps bf16 rows for its backward, would cost ~4x the feature error).
+`freeze_backbone_bn = True` is a deliberate deviation: the folded-BatchNorm inference path in train mode, running statistics untouched (the usual way to fine-tune on a
+frozen backbone).  The LSTM and the head run as autograd ops over HIP kernels
+(autograd_ops.lstm_layer / mlp_head); dropout masks come from torch's RNG.
+
+State dict keys are the reference's (resnet50.<child>..., lstm.*, classifier.*).
+"""
+from __future__ import annotations
+
+from collections import OrderedDict
+
+import numpy as np
+import torch
+
+from . import autograd_ops as A
+from . import ops
+from .resnet3d import ResNet3d, _ru
+from .weights import RESNET50_2D, blocks_to_torchvision_resnet50, resnet50_lstm_param_shapes, \
+    torchvision_resnet50_to_blocks
+
+HEAD_DIM = 64  # classifier.0: Linear(hidden, 64)
+
+
+class VideoResNet50LSTM(torch.nn.Module):
+    def __init__(self, hidden_size: int = 256, num_layers: int = 2, dropout: float = 0.5,
+                 freeze_backbone_bn: bool = False):
+        super().__init__()
+        if hidden_size <= 0 or hidden_size % 4 or hidden_size > 1024:
+            raise ValueError(f"hidden_size {hidden_size} unsupported: hidden_size % 4 == 0 and hidden_size <= 1024")
+        if num_layers < 1:
+            raise ValueError("num_layers must be >= 1")
+        if not 0.0 <= dropout < 1.0:
+            raise ValueError("dropout must be in [0, 1)")
+        self.hidden, self.layers, self.dropout = hidden_size, num_layers, float(dropout)
+        # False (the reference): model.train() runs the frozen backbone's BatchNorm with batch statistics and
+        # updates its running statistics; True: the folded inference path, running statistics untouched
+        self.freeze_backbone_bn = freeze_backbone_bn
+        self.backbone = ResNet3d(RESNET50_2D)
+        for p in self.backbone.parameters():
+            p.requires_grad_(False)  # model.py:15-16
+        shapes = resnet50_lstm_param_shapes(hidden_size, num_layers)
+        self._all_names = list(shapes.keys())
+        self._names = [n for n in shapes if not n.startswith("resnet50.")]
+        self.params = torch.nn.ParameterDict()
+        for n in self._names:
+            self.params[n.replace(".", "__")] = torch.nn.Parameter(torch.zeros(shapes[n]), requires_grad=True)
+        self._packed = None
+        self._ws = {}
+        # the last forward's bf16 feature matrix [B*T, 2048] and dropout masks ({"lstm": [per layer or None],
+        # "head": mask or None}), for tests that replay them through an oracle
+        self.last_features = None
+        self.last_keep = None
+
+    def P(self, name):
+        return self.params[name.replace(".", "__")]
+
+    # ---- state dict in the reference's naming -----------------------------------------
+    def state_dict(self, *a, **k):
+        bb = self.backbone.state_dict()
+        out = OrderedDict()
+        for n in self._all_names:
+            if n.startswith("resnet50."):
+                v = bb[torchvision_resnet50_to_blocks(n)]
+                out[n] = v.squeeze(2) if v.dim() == 5 else v
+            else:
+                out[n] = self.P(n).detach()
+        return out
+
+    def load_state_dict(self, sd, strict: bool = True):
+        sd = {k[len("module."):] if k.startswith("module.") else k: v for k, v in sd.items()}
+        bb, rest = {}, {}
+        for k, v in sd.items():
+            if k.endswith("num_batches_tracked"):
+                continue
+            b = torchvision_resnet50_to_blocks(k)
+            if b is not None:
+                v = torch.as_tensor(np.asarray(v)) if not isinstance(v, torch.Tensor) else v
+                bb[b] = v.unsqueeze(2) if v.dim() == 4 else v
+            else:
+                rest[k] = v
+        missing = [n for n in self._names if n not in rest]
+        unexpected = [k for k in rest if k not in self._names]
+        if strict and (missing or unexpected):
+            raise KeyError(f"load_state_dict: missing={missing[:5]} unexpected={unexpected[:5]}")
+        m1, u1 = self.backbone.load_state_dict(bb, strict=strict)
+        m1 = [blocks_to_torchvision_resnet50(n) for n in m1]
+        with torch.no_grad():
+            for n in self._names:
+                if n in rest:
+                    v = rest[n]
+                    v = torch.as_tensor(np.asarray(v)) if not isinstance(v, torch.Tensor) else v
+                    self.P(n).copy_(v.reshape(self.P(n).shape))
+        self._packed = None
+        return m1 + missing, u1 + unexpected
+
+    # ---- operand images of the LSTM / head weights, once per weights version -----------
+    def _weights_version(self):
+        from . import vivit_train
+        return (vivit_train.MASTER_EPOCH[0], sum(p._version for p in self.params.values()))
+
+    def _pack(self, device):
+        ver = self._weights_version()  # the fused AdamW updates in place without bumping _version
+        if self._packed is not None and self._packed["device"] == device and self._packed["version"] == ver:
+            return self._packed
+        pk = {"device": device, "version": ver, "layers": []}
+        for l in range(self.layers):
+            L = A.pack_lstm_weights(self.P(f"lstm.weight_ih_l{l}"), self.P(f"lstm.weight_hh_l{l}"))
+            b = torch.zeros(L["wb"].shape[0], dtype=torch.float32, device=device)
+            b[: 4 * self.hidden] = self.P(f"lstm.bias_ih_l{l}").detach() + self.P(f"lstm.bias_hh_l{l}").detach()
+            L["b"] = b
+            pk["layers"].append(L)
+        pk["head"] = [self.P(n).detach().float().contiguous() for n in
+                      ("classifier.0.weight", "classifier.0.bias", "classifier.3.weight", "classifier.3.bias")]
+        self._packed = pk
+        return pk
+
+    def _workspace(self, B, T, device):
+        key = (B, T, str(device))
+        if key not in self._ws:
+            M = _ru(B * T, 256)
+            z = lambda r, c, dt: torch.zeros(r, c, dtype=dt, device=device)  # noqa: E731
+            self._ws = {key: dict(pre=z(M, _ru(4 * self.hidden, 128), torch.float32),
+                                  hseq=[z(M, _ru(self.hidden, 128), torch.bfloat16) for _ in range(2)],
+                                  hlast=z(B, self.hidden, torch.float32), logits=z(B, 1, torch.float32))}
+        return self._ws[key]
+
+    # ---- forward -----------------------------------------------------------------------
+    def forward(self, video: torch.Tensor) -> torch.Tensor:
+        """`model(video)` -> logits f32 [B, 1].  In training mode the train step runs (batch-statistic
+        BatchNorm in the frozen backbone unless `freeze_backbone_bn`, dropout, autograd ops), with
+        autograd enabled or not; in eval mode the fused inference path."""
+        if not isinstance(video, torch.Tensor) or video.device.type != "cuda":
+            raise RuntimeError("VideoResNet50LSTM (vclip_amd) runs on the GPU only: move the clip batch to cuda")
+        if video.dim() != 5 or video.shape[1] != 3:
+            raise ValueError("video must be [B, 3, T, H, W]")
+        x = video.contiguous().float() if video.dtype != torch.float32 else video.contiguous()
+        if self.training:
+            return self._forward_train(x)
+        with torch.no_grad():
+            return self.forward_logits(x).clone()  # the workspace buffer is reused by the next call
+
+    def features(self, video: torch.Tensor, train_bn: bool = False) -> torch.Tensor:
+        """Per-frame ResNet-50 features bf16 [ru(B*T, 256), 2048] (rows >= B*T are zero)."""
+        B, _, T = video.shape[:3]
+        with torch.no_grad():
+            if train_bn:
+                x, (t, h, w), Cf = self._train_features_h16(video)
+                self.backbone._packed = None  # the running statistics moved: re-fold before the next eval
+            else:
+                x, _, (t, h, w), Cf, _ = self.backbone.forward_features(video)
+            feat = torch.zeros(_ru(B * T, 256), Cf, dtype=torch.bfloat16, device=video.device)
+            # per-frame AdaptiveAvgPool2d(1): rows are ((b*T + t)*h + y)*w + x
+            ops.frame_avgpool(x, B * T, h * w, Cf, feat)
+        self.last_features = feat[: B * T]
+        return feat
+
+    # ---- the frozen backbone in train mode: batch-statistic BatchNorm, no gradients, fp16 rows -----
+    def _backbone_h16(self, device):
+        """fp16 images [ru(Cout, 128), ru(K, 128)] of the conv weights, columns (kt, kh, kw, c) with the
+        stem's 3 input channels padded to 8; once per backbone weights version."""
+        ver = self.backbone._weights_version()
+        pk = getattr(self, "_bb_h16", None)
+        if pk is not None and pk["device"] == device and pk["version"] == ver:
+            return pk
+        pk = {"device": device, "version": ver}
+        for n in self.backbone._names:
+            if self.backbone.P(n).dim() != 5:  # conv weights only
+                continue
+            w = self.backbone.P(n).detach().to(device).permute(0, 2, 3, 4, 1)  # [Co, kt, kh, kw, Ci]
+            if w.shape[-1] % 8:
+                w = torch.nn.functional.pad(w, (0, 8 - w.shape[-1] % 8))
+            w = w.reshape(w.shape[0], -1)
+            img = torch.zeros(_ru(w.shape[0], 128), _ru(w.shape[1], 128), dtype=torch.float16, device=device)
+            img[: w.shape[0], : w.shape[1]] = w
+            pk[n] = img
+        self._bb_h16 = pk
+        return pk
+
+    def _train_features_h16(self, video: torch.Tensor):
+        """torchvision's ResNet-50 in training mode without gradients (the reference's frozen backbone under
+        model.train()): every conv is an fp16 MFMA GEMM with fp32 accumulation, BatchNorm takes its batch
+        statistics in fp32 and updates the running ones (vc_batchnorm_train_fwd), and the activations
+        stay fp16 rows (vc_bn_apply_h16).  ResNet3d's own train-mode forward keeps bf16 rows for its
+        backward; here nothing is differentiated and bf16 rows would cost ~4x the feature error, because
+        the batch-statistic normalisation amplifies storage rounding.
+        fp16 tops out at 65504 where bf16 does not: every stored row here is a BatchNorm output (|z| of
+        order gamma * a few + beta) or the normalised input clip, and the GEMMs accumulate and leave in
+        fp32, so only a checkpoint with BatchNorm gains of order 1e4 could reach it.  The accumulate
+        epilogue is the fp16 GEMM's only fp32-output one, hence the zeroed `y`.
+        Returns (last activations fp16 [>= B*T*h*w, 2048], (T, h, w), 2048)."""
+        bb = self.backbone
+        c, P = bb.cfg, bb.P
+        B, _, T, H, W = video.shape
+        dev = video.device
+        wts = self._backbone_h16(dev)
+        stem, grids = bb.geometry(T, H, W)
+        f16, bf16 = torch.float16, torch.bfloat16
+        eps = c["bn_eps"]
+
+        def conv_bn(x, grid, cin, conv, bn, kernel, stride, pad, relu, res=None):
+            w16 = wts[conv + ".weight"]
+            cout = P(conv + ".weight").shape[0]
+            go = ops.conv_out_size(grid, kernel, stride, pad)
+            M = B * go[0] * go[1] * go[2]
+            Mp, (Np, Kp) = _ru(M, 256), w16.shape
+            if tuple(kernel) == (1, 1, 1) and tuple(stride) == (1, 1, 1) and tuple(x.shape) == (Mp, Kp):
+                a = x
+            else:  # the 16-bit patch gather is element-type agnostic
+                kk = kernel[0] * kernel[1] * kernel[2] * cin  # columns past it meet zero weights: keep them finite
+                a = (torch.zeros if kk != Kp else torch.empty)(Mp, Kp, dtype=f16, device=dev)
+                ops.conv3d_im2col(x.view(bf16), "cl_bf16", B, grid, cin, kernel, stride, pad, a.view(bf16))
+            y = torch.zeros(Mp, Np, dtype=torch.float32, device=dev)
+            ops.gemm(a, w16, A._zeros_f32(Np, dev), "bias_resid_f32", y, op="backbone_train")
+            g, b = P(bn + ".weight").detach(), P(bn + ".bias").detach()
+            stat = torch.empty(2, cout, dtype=torch.float32, device=dev)
+            ops.batchnorm_train_stats(y[:M, :cout], g, b, P(bn + ".running_mean").detach(),
+                                      P(bn + ".running_var").detach(), stat, eps=eps, momentum=0.1)
+            z = (torch.zeros if cout % 128 else torch.empty)(Mp, _ru(cout, 128), dtype=f16, device=dev)
+            ops.bn_apply_h16(y[:M, :cout], stat, g, b, z, res=res, relu=relu)
+            return z, go, cout
+
+        xcl = torch.empty(B * T * H * W, 8, dtype=f16, device=dev)
+        ops.video_to_cl_h16(video, xcl)
+        x, g0, cin = conv_bn(xcl, (T, H, W), 8, "blocks.0.conv", "blocks.0.norm", c["stem_kernel"], (1, 2, 2),
+                             c["stem_pad"], True)
+        # MaxPool on non-negative (post-ReLU) rows: 16-bit floats of one sign order like their bit patterns,
+        # in fp16 as in bf16, so the bf16 kernel returns the exact fp16 maxima
+        gm = grids[0]
+        xm = torch.zeros(_ru(B * gm[0] * gm[1] * gm[2], 256), x.shape[1], dtype=f16, device=dev)
+        ops.maxpool3d(x.view(bf16), B, g0, cin, (1, 3, 3), (1, 2, 2), (0, 1, 1), xm.view(bf16))
+        x, g_in = xm, gm
+        for s, depth in enumerate(c["depths"]):
+            ss = c["spatial_strides"][s]
+            for i in range(depth):
+                p = f"blocks.{s + 1}.res_blocks.{i}."
+                stride = (1, ss, ss) if i == 0 else (1, 1, 1)
+                sc = x
+                if p + "branch1_conv.weight" in bb._names:
+                    sc, _, _ = conv_bn(x, g_in, cin, p + "branch1_conv", p + "branch1_norm", (1, 1, 1), stride,
+                                       (0, 0, 0), False)
+                ya, _, ci = conv_bn(x, g_in, cin, p + "branch2.conv_a", p + "branch2.norm_a", (1, 1, 1), (1, 1, 1),
+                                    (0, 0, 0), True)
+                yb, g, ci = conv_bn(ya, g_in, ci, p + "branch2.conv_b", p + "branch2.norm_b", (1, 3, 3), stride,
+                                    (0, 1, 1), True)
+                x, _, cin = conv_bn(yb, g, ci, p + "branch2.conv_c", p + "branch2.norm_c", (1, 1, 1), (1, 1, 1),
+                                    (0, 0, 0), True, res=sc)
+                g_in = g
+        return x, g_in, cin
+
+    def forward_logits(self, video: torch.Tensor) -> torch.Tensor:
+        """Inference: logits f32 [B, 1] (a workspace buffer, overwritten by the next call)."""
+        B, _, T = video.shape[:3]
+        pk = self._pack(video.device)
+        ws = self._workspace(B, T, video.device)
+        inp = self.features(video)
+        for l, L in enumerate(pk["layers"]):
+            ops.gemm(inp, L["wb"], L["b"], "bias_f32", ws["pre"], op="lstm_ih")
+            ops.lstm_seq_fwd(ws["pre"], B, T, self.hidden, L["w_hh_t"], ws["hseq"][l & 1], ws["hlast"])
+            inp = ws["hseq"][l & 1]
+        w1, b1, w2, b2 = pk["head"]
+        return ops.mlp_head_fwd(ws["hlast"], w1, b1, w2, b2, ws["logits"])
+
+    def _forward_train(self, video: torch.Tensor) -> torch.Tensor:
+        B, _, T = video.shape[:3]
+        return self._forward_tail(self.features(video, train_bn=not self.freeze_backbone_bn)[: B * T], B, T)
+
+    def _forward_tail(self, x: torch.Tensor, B: int, T: int) -> torch.Tensor:
+        """The trainable part of the train step on the bf16 features [B*T, 2048]: the LSTM layers and the
+        head as autograd ops, with their dropout masks."""
+        dev = x.device
+        pk = self._pack(dev)
+        p = self.dropout
+        keeps = []
+        h_last = None
+        for l in range(self.layers):
+            top = l == self.layers - 1
+            keep = None
+            if p > 0.0 and not top:  # nn.LSTM: dropout on the outputs of every layer but the last
+                keep = torch.ones(B * T, self.hidden, device=dev).bernoulli_(1.0 - p).mul_(1.0 / (1.0 - p))
+            keeps.append(keep)
+            x, h_last = A.lstm_layer(x, self.P(f"lstm.weight_ih_l{l}"), self.P(f"lstm.weight_hh_l{l}"),
+                                     self.P(f"lstm.bias_ih_l{l}"), self.P(f"lstm.bias_hh_l{l}"), B, T, keep=keep,
+                                     last_only=top, need_dx=l > 0, packed=pk["layers"][l])
+        hkeep = None
+        if p > 0.0:
+            hkeep = torch.ones(B, HEAD_DIM, device=dev).bernoulli_(1.0 - p).mul_(1.0 / (1.0 - p))
+        self.last_keep = {"lstm": keeps, "head": hkeep}
+        return A.mlp_head(h_last, self.P("classifier.0.weight"), self.P("classifier.0.bias"),
+                          self.P("classifier.3.weight"), self.P("classifier.3.bias"), hkeep)
+
+
+def create_model(hidden_size: int = 256, num_layers: int = 2, dropout: float = 0.5, device="cuda",
+                 weights_seed: int = 0):
+    """VideoResNet50LSTM with seeded synthetic weights (the reference loads torchvision's
+    IMAGENET1K_V1 ResNet-50, unavailable offline; load a checkpoint with load_state_dict)."""
+    from .weights import make_resnet50_lstm_weights
+    m = VideoResNet50LSTM(hidden_size, num_layers, dropout)
+    sd = make_resnet50_lstm_weights(seed=weights_seed, hidden=hidden_size)
+    if num_layers != 2:  # the seeded weights cover two layers: further layers keep layer 1's distribution
+        rng = np.random.RandomState(weights_seed + 2)
+        k = 1.0 / np.sqrt(hidden_size)
+        shapes = resnet50_lstm_param_shapes(hidden_size, num_layers)
+        sd = OrderedDict((n, sd[n] if n in sd else rng.uniform(-k, k, shapes[n]).astype(np.float32)) for n in shapes)
+    m.load_state_dict(sd)
+    return m.to(device) if device else m

@@ -402,7 +402,8 @@ int vc_maxpool3d_bwd(const uint16_t* x, int64_t ldx, const void* dy, int dy_bf16
  * biased variance (two passes, fixed-order reductions) -> stat f32 [2][C] = {mean, rstd}; the
  * running statistics (if given) updated with `momentum` and the unbiased variance; z bf16 =
  * relu?(gamma * (y - mean) * rstd + beta (+ res: bf16 if res_bf16 else f32)).  work >= 2*C*splits
- * floats (splits = clamp(ceil(M / 128), 1, 4096)). */
+ * floats (splits = clamp(ceil(M / 128), 1, 4096)).  z == NULL: statistics only (stat and the running
+ * statistics are written, nothing else; vc_bn_apply_h16 then writes fp16 rows from stat). */
 int vc_batchnorm_train_fwd(const float* y, int64_t ldy, int64_t M, int64_t C, const float* gamma, const float* beta,
                            float eps, float momentum, float* running_mean, float* running_var, const void* res,
                            int res_bf16, int64_t ldr, int relu, uint16_t* z, int64_t ldz, float* stat, float* work,
@@ -649,6 +650,77 @@ int vc_adamw_multi(const int64_t* table, int64_t ntab, int64_t nchunks, float lr
  */
 int vc_pack_weight(const float* src, int64_t N, int64_t K, int64_t nscaled, float scale, uint16_t* dst, uint16_t* dstT,
                    hipStream_t stream);
+
+/* ---- ResNet50-LSTM (resnet50-2d-lstm/src/models/model.py:5-60, trainer.py:156-170), csrc/lstm.hip ---- */
+
+/*
+ * Per-frame AdaptiveAvgPool2d(1) on channels-last bf16 rows: out[n][c] = mean over p < P of
+ * x[n*P + p][c], summed in fp32, rounded once to bf16 (the operand of the first LSTM GEMM).
+ * elem_type: the rows of x are VC_ELEM_BF16 or VC_ELEM_F16.
+ */
+int vc_frame_avgpool(const uint16_t* x, int elem_type, int64_t ldx, int64_t N, int64_t P, int64_t C, uint16_t* out,
+                     int64_t ldo, hipStream_t stream);
+
+/*
+ * The two fp16 pieces of the frozen ResNet-50's train-mode forward (batch-statistic BatchNorm without
+ * gradients, activations kept in fp16: bf16 rows cost ~4x the feature error there).
+ * vc_bn_apply_h16: z fp16 [M][C] = relu?(gamma (y - mean) rstd + beta (+ res fp16)), stat = [mean | rstd]
+ * f32 [2][C] as vc_batchnorm_train_fwd leaves it (that entry computes the statistics and updates the
+ * running ones).  C % 4 == 0.
+ * vc_video_to_cl_h16: f32 clip [B][C][P] -> channels-last fp16 rows [B*P][8], channels >= C zero (C <= 8).
+ */
+int vc_bn_apply_h16(const float* y, int64_t ldy, int64_t M, int64_t C, const float* stat, const float* gamma,
+                    const float* beta, const uint16_t* res, int64_t ldr, int relu, uint16_t* z, int64_t ldz,
+                    hipStream_t stream);
+int vc_video_to_cl_h16(const float* x, int64_t B, int64_t C, int64_t P, uint16_t* out, hipStream_t stream);
+
+/*
+ * All T steps of one nn.LSTM layer (batch_first, h_0 = c_0 = 0) in one launch.
+ *   pre     f32 [B*T][4*hidden] (row b*T + t, stride ldpre) = x_t W_ih^T + b_ih + b_hh, gate order i, f, g, o;
+ *   W_hh_t  f32 [hidden][4*hidden], the TRANSPOSE of weight_hh (read coalesced);
+ *   h_seq   bf16 [B*T][hidden] (stride ldh): h_t, times keep[b*T + t][j] when keep != NULL
+ *           (f32 [B*T][hidden], nn.LSTM's inter-layer dropout mask already scaled by 1 / (1 - p));
+ *           the recurrent h is never masked;
+ *   h_last  f32 [B][hidden] = h_{T-1}, unmasked.
+ * Train variant (gates != NULL; then c_seq and h_prev are required): also writes the post-activation
+ * gates f32 [B*T][4*hidden], c_seq f32 [B*T][hidden] and h_prev bf16 [B*T][hidden] (stride ldhp) =
+ * h_{t-1}, zero at t = 0 (the operand of the W_hh gradient).  h is bit-identical in both variants.
+ * A workgroup owns 4 whole sequences (2 for hidden > 512): no cross-workgroup synchronisation.
+ * All arithmetic fp32; deterministic.  hidden % 4 == 0, hidden <= 1024; any B, T >= 1.
+ */
+int vc_lstm_seq_fwd(const float* pre, int64_t ldpre, int64_t B, int64_t T, int64_t hidden, const float* W_hh_t,
+                    const float* keep, uint16_t* h_seq, int64_t ldh, float* h_last, float* gates, float* c_seq,
+                    uint16_t* h_prev, int64_t ldhp, hipStream_t stream);
+
+/*
+ * Its backward through time, t = T-1 .. 0 in one launch, from the saved gates and c_seq.
+ *   W_hh    f32 [4*hidden][hidden], natural layout;
+ *   dh      last_only = 0: f32 [B*T][hidden] (row b*T + t, stride lddh), dL/d(h_seq);
+ *           last_only = 1: f32 [B][hidden] (stride lddh), dL/d(h_last): only step T-1 carries gradient;
+ *   keep    optional, as in the forward: the incoming dh row of step t is multiplied by keep[b*T + t].
+ * Writes dpre f32 [B*T][4*hidden] (dL/d pre) and dpre_bf16 (stride lddb), its bf16 copy for the
+ * weight / input gradient GEMMs: dW_ih = dpre^T x, dW_hh = dpre^T h_prev, db = colsum(dpre), dx = dpre W_ih.
+ * Same shapes, grouping and determinism as vc_lstm_seq_fwd.
+ */
+int vc_lstm_seq_bwd(const float* gates, const float* c_seq, int64_t B, int64_t T, int64_t hidden, const float* W_hh,
+                    const float* dh, int64_t lddh, int last_only, const float* keep, float* dpre, uint16_t* dpre_bf16,
+                    int64_t lddb, hipStream_t stream);
+
+/*
+ * The classifier Linear(hidden, H1) -> ReLU -> Dropout -> Linear(H1, num_labels) on f32 h [B][hidden]:
+ * hid[b][r] = relu(W1[r] . h[b] + b1[r]) * keep[b][r] (keep f32 [B][H1] = 0 or 1 / (1 - p); NULL = no
+ * dropout), logits[b][c] = W2[c] . hid[b] + b2[c].  hid (optional, f32 [B][H1]) is saved for the
+ * backward.  hidden, H1, num_labels <= 1024.
+ */
+int vc_mlp_head_fwd(const float* h, int64_t B, int64_t hidden, const float* W1, const float* b1, int64_t H1,
+                    const float* keep, const float* W2, const float* b2, int64_t num_labels, float* hid, float* logits,
+                    hipStream_t stream);
+
+/* Its backward from dlogits f32 [B][num_labels] and the saved hid: dh [B][hidden], dW1 [H1][hidden],
+ * db1 [H1], dW2 [num_labels][H1], db2 [num_labels] (all f32, overwritten; sums in index order). */
+int vc_mlp_head_bwd(const float* h, const float* W1, const float* W2, const float* hid, const float* keep,
+                    const float* dlogits, int64_t B, int64_t hidden, int64_t H1, int64_t num_labels, float* dh, float* dW1,
+                    float* db1, float* dW2, float* db2, hipStream_t stream);
 
 #ifdef __cplusplus
 }
