@@ -6,6 +6,9 @@
   timesformer/main.py, inference.py  timesformer_main / timesformer_inference
   videoswintransformer/...           swin_main / swin_inference
   resnet50-3d-video/...              resnet3d_main / resnet3d_inference
+  resnet50-2d-lstm/...               run_main_lstm / run_inference_lstm: that folder's own flags, loop and
+                                     outputs (the last section of this file); inference over a directory
+                                     of videos, several per forward (VideoResNet50LSTM.forward_ragged)
 
 Launchers with the reference's folder layout live in `cli/<folder>/{main,inference}.py`.
 Sampling is the bit-exact host sampler of each folder (vclip_amd.sampling); decode is host work
@@ -200,10 +203,14 @@ FAMILIES = {
     "timesformer": Family("timesformer", "timesformer-classifier", "timesformer-models", 4, 40, 1e-3, 0.01, "adamw"),
     "swin": Family("swin", "swin3d-classifier", "swin-models", 8, 30, 1e-4, 0.05, "adamw"),
     "resnet3d": Family("resnet3d", "resnet3d-classifier", "resnet3d-models", 8, 30, 1e-3, 0.0, "adam"),
+    # resnet50-2d-lstm: its own flags, loop and outputs (build_parser_lstm, run_main_lstm, run_inference_lstm)
+    "lstm": Family("lstm", "resnet50_lstm_enhanced", "models", 4, 30, 1e-3, 0.0, "adam"),
 }
 
 
 def build_parser(fam: Family, inference: bool):
+    if fam.name == "lstm":
+        return build_parser_lstm(inference)
     p = argparse.ArgumentParser(description=f"{fam.name} video classifier (libvclip, MI355X)")
     if inference:
         p.add_argument("--video_path", type=str, required=True)
@@ -348,6 +355,8 @@ def evaluate(fam, model, loader, args, device, class_names, exp_dir, method, log
 
 
 def run_main(fam_name, argv=None):
+    if fam_name == "lstm":
+        return run_main_lstm(argv)
     fam = FAMILIES[fam_name]
     args = build_parser(fam, inference=False).parse_args(argv)
     torch.manual_seed(args.seed)
@@ -444,6 +453,8 @@ def run_main(fam_name, argv=None):
 
 
 def run_inference(fam_name, argv=None):
+    if fam_name == "lstm":
+        return run_inference_lstm(argv)
     fam = FAMILIES[fam_name]
     args = build_parser(fam, inference=True).parse_args(argv)
     exp = ExperimentLogger(args.log_dir, prefix=f"{fam.prefix}-inference")
@@ -510,3 +521,475 @@ class _SwinInferenceSampler:
     def get_sampling_indices(self, video_path, total_frames):
         return sampling.swin_inference_sampling_indices(video_path, total_frames, self.num_frames, self.method,
                                                         self.logger, fps_of=lambda p: self.fps)
+
+
+# ------------------------------------------------------------------------- resnet50-2d-lstm
+# The fifth folder's application is its own: one logit under BCEWithLogitsLoss(pos_weight), Adam over the
+# trainable parameters, ReduceLROnPlateau on the validation AUROC, a composite (loss, AUROC) model
+# selection, plain state_dict checkpoints, and an inference script that walks a directory of videos
+# (resnet50-2d-lstm/main.py, src/trainer/trainer.py, src/evaluators/evaluator.py, inference.py).
+LSTM_SEED = 42  # src/config/config.py:4
+LSTM_CLASS_NAMES = ["non_referral", "referral"]
+LSTM_HISTORY_KEYS = ("train_loss", "val_loss", "train_acc", "val_acc", "train_auroc", "val_auroc")
+# batched ragged inference: the smallest batch within 5 % of the best measured rate, which was the largest
+# measured (16 videos per call 2211 videos/s, 8 per call 1907, one at a time 656)
+LSTM_VIDEOS_PER_BATCH = 16
+
+
+def build_parser_lstm(inference: bool):
+    sampling3 = ["uniform", "random", "random_window"]
+    if inference:  # resnet50-2d-lstm/inference.py:206-223
+        p = argparse.ArgumentParser(description="ResNet50-LSTM inference over a directory of videos (libvclip, MI355X)")
+        p.add_argument("--videos_dir", type=str, required=True)
+        p.add_argument("--model_path", type=str, required=True)
+        p.add_argument("--output_dir", type=str, default="inference_results")
+        p.add_argument("--sampling_method", type=str, default="uniform", choices=sampling3)
+        p.add_argument("--sequence_length", type=int, default=32)
+        p.add_argument("--visualize", action="store_true")
+        p.add_argument("--batch_mode", action="store_true")
+        p.add_argument("--single_video", type=str, default=None)
+        # not in the reference, which runs one video per forward: videos per forward_ragged call
+        p.add_argument("--videos_per_batch", type=int, default=LSTM_VIDEOS_PER_BATCH)
+        return p
+    p = argparse.ArgumentParser(description="ResNet50-LSTM video classification training (libvclip, MI355X)")
+    p.add_argument("--data_dir", type=str, default="dataset")  # resnet50-2d-lstm/main.py:22-62
+    p.add_argument("--test_dir", type=str, default=None)
+    p.add_argument("--log_dir", type=str, default="logs")
+    p.add_argument("--model_dir", type=str, default="models")
+    for s in ("train", "val", "test"):
+        p.add_argument(f"--{s}_sampling", type=str, default="uniform", choices=sampling3)
+    p.add_argument("--loss_weight", type=float, default=0.3)
+    p.add_argument("--learning_rate", type=float, default=0.001)
+    p.add_argument("--batch_size", type=int, default=4)
+    p.add_argument("--epochs", type=int, default=30)
+    p.add_argument("--patience", type=int, default=10)
+    p.add_argument("--hidden_size", type=int, default=256)
+    p.add_argument("--num_layers", type=int, default=2)
+    p.add_argument("--dropout", type=float, default=0.5)
+    p.add_argument("--sequence_length", type=int, default=32)
+    p.add_argument("--skip_train", action="store_true")
+    p.add_argument("--checkpoint_path", type=str, default=None)
+    p.add_argument("--num_workers", type=int, default=2)
+    return p
+
+
+class LstmExperimentLogger:
+    """src/utils/logger.py:6-58: the given directory itself is the experiment directory, log file
+    `<prefix>.log`."""
+
+    def __init__(self, log_dir, prefix="resnet50-lstm-training"):
+        self.exp_dir = Path(log_dir)
+        if self.exp_dir.exists() and not self.exp_dir.is_dir():
+            raise ValueError(f"Log directory path exists but is not a directory: {log_dir}")
+        self.exp_dir.mkdir(parents=True, exist_ok=True)
+        self.logger = logging.getLogger(f"ResNet50LSTM-{id(self)}")
+        self.logger.setLevel(logging.INFO)
+        self.logger.propagate = False
+        fh = logging.FileHandler(self.exp_dir / f"{prefix}.log")
+        fh.setFormatter(logging.Formatter("%(asctime)s - %(levelname)s - %(message)s"))
+        ch = logging.StreamHandler()
+        ch.setFormatter(logging.Formatter("%(levelname)s: %(message)s"))
+        self.logger.addHandler(fh)
+        self.logger.addHandler(ch)
+        self.logger.info(f"Experiment directory created: {self.exp_dir}")
+
+    def get_logger(self):
+        return self.logger
+
+    def get_experiment_dir(self):
+        return self.exp_dir
+
+
+def lstm_pos_weight(labels) -> float:
+    """trainer.py:35-41: (n / (2 n1)) / (n / (2 n0)) * 1.5 from the train split's labels."""
+    n = len(labels)
+    n1 = int(sum(labels))
+    n0 = n - n1
+    if n1 == 0:
+        raise ValueError("pos_weight is undefined: the train split holds no 'referral' video (label 1)")
+    if n0 == 0:
+        raise ValueError("pos_weight is undefined: the train split holds no 'non_referral' video (label 0)")
+    return n / (2 * n1) / (n / (2 * n0)) * 1.5
+
+
+class LstmModelSelector:
+    """trainer.py:66-77, 99-122, 288-298: the composite (loss, AUROC) model selection and the early-stopping
+    counter.  `update(val_loss, val_auroc)` -> True when the model is the best so far (save it)."""
+
+    def __init__(self, loss_weight=0.3, patience=10):
+        self.loss_weight, self.auroc_weight = loss_weight, 1.0 - loss_weight
+        self.patience = patience
+        self.best_composite_score = -float("inf")
+        self.best_val_loss = float("inf")
+        self.best_val_auroc = 0.0
+        self.counter = 0
+        self.early_stop = False
+
+    def should_save(self, val_loss, val_auroc):
+        best_val_loss = min(self.best_val_loss, val_loss)
+        normalized_loss = best_val_loss / max(val_loss, 1e-10)
+        composite_score = self.loss_weight * normalized_loss + self.auroc_weight * val_auroc
+        if composite_score > self.best_composite_score:
+            self.best_composite_score = composite_score
+            self.best_val_loss = val_loss
+            self.best_val_auroc = val_auroc
+            return True
+        return False
+
+    def update(self, val_loss, val_auroc):
+        if self.should_save(val_loss, val_auroc):
+            self.counter = 0
+            return True
+        self.counter += 1
+        if self.counter >= self.patience:
+            self.early_stop = True
+        return False
+
+
+def _lstm_auroc(labels, scores, what, logger):
+    """roc_auc_score, or 0.5 when the epoch saw one class only (the reference raises there and the per-epoch
+    code has no handler: a deliberate deviation, logged)."""
+    from sklearn.metrics import roc_auc_score
+    if len(np.unique(labels)) < 2:
+        logger.warning(f"{what} AUROC is undefined (one class only in this epoch): recording 0.5")
+        return 0.5
+    return float(roc_auc_score(labels, scores))
+
+
+def lstm_test_metrics(labels, preds, probs, class_names, logger):
+    """evaluator.py:102-173: the dict written to test_metrics.json."""
+    from sklearn.metrics import accuracy_score, confusion_matrix, f1_score, precision_score, recall_score, roc_auc_score
+    labels, preds = np.asarray(labels, dtype=np.int64), np.asarray(preds, dtype=np.int64)
+    probs = np.asarray(probs, dtype=np.float64)
+    try:
+        auroc = roc_auc_score(labels, probs)
+        if not np.isfinite(auroc):
+            raise ValueError("one class only")
+    except Exception as e:  # noqa: BLE001 - evaluator.py:104-108
+        logger.error(f"Error calculating AUROC: {str(e)}")
+        auroc = 0.5
+    class_metrics = {}
+    for ci, name in enumerate(class_names):
+        mask = labels == ci
+        class_metrics[name] = {
+            "accuracy": float(accuracy_score(mask[mask], preds[mask] == ci)) if np.any(mask) else 0.0,
+            "precision": float(precision_score(labels, preds, pos_label=ci, zero_division=0)),
+            "recall": float(recall_score(labels, preds, pos_label=ci, zero_division=0)),
+            "f1_score": float(f1_score(labels, preds, pos_label=ci, zero_division=0))}
+    return {"auroc": float(auroc), "f1_score": float(f1_score(labels, preds, zero_division=0)),
+            "accuracy": float(accuracy_score(labels, preds)),
+            "precision": float(precision_score(labels, preds, zero_division=0)),
+            "recall": float(recall_score(labels, preds, zero_division=0)),
+            "confusion_matrix": confusion_matrix(labels, preds).tolist(), "class_metrics": class_metrics}
+
+
+def _lstm_load_state(model, path, logger):
+    sd = torch.load(path, map_location="cpu", weights_only=True)  # a plain state_dict (trainer.py:290)
+    model.load_state_dict(sd)
+    logger.info(f"Loaded weights from {path}")
+
+
+def _lstm_epoch(model, loader, crit, device, opt, logger, what):
+    """One pass over a loader (trainer.py:146-199 with `opt`, :202-249 without): (loss, acc, auroc, number of
+    videos seen).  A failing batch is logged and skipped."""
+    from sklearn.metrics import accuracy_score
+    total, scores, labels_all = 0.0, [], []
+    for videos, labels in loader:
+        try:
+            videos, labels = videos.to(device), labels.to(device)
+            if opt is not None:
+                opt.zero_grad()
+            outputs = model(videos)
+            loss = crit(outputs, labels.unsqueeze(1))
+            if opt is not None:
+                loss.backward()
+                opt.step()
+            total += loss.item() * videos.size(0)
+            scores.extend(torch.sigmoid(outputs.detach()).float().cpu().numpy().reshape(-1))
+            labels_all.extend(labels.cpu().numpy().reshape(-1))
+        except Exception as e:  # noqa: BLE001
+            logger.error(f"Error in {what} batch: {str(e)}")
+            continue
+    n = len(labels_all)
+    if n == 0:
+        return 0.0, 0.0, 0.5, 0
+    scores, labels_all = np.asarray(scores), np.asarray(labels_all)
+    preds = (scores >= 0.5).astype(int)
+    return total / n, float(accuracy_score(labels_all, preds)), _lstm_auroc(labels_all, scores, what, logger), n
+
+
+@torch.no_grad()
+def evaluate_lstm(model, loader, device, exp_dir, logger, class_names=None):
+    """evaluator.py:24-173 without the plots: sigmoid, threshold 0.5, test_metrics.json."""
+    class_names = class_names or LSTM_CLASS_NAMES
+    model.eval()
+    preds, labels_all, probs = [], [], []
+    logger.info("Starting model evaluation...")
+    for i, (videos, labels) in enumerate(loader):
+        try:
+            p = torch.sigmoid(model(videos.to(device))).float().cpu().numpy().reshape(-1)
+            probs.extend(p)
+            preds.extend((p >= 0.5).astype(int))
+            labels_all.extend(labels.cpu().numpy().reshape(-1))
+        except Exception as e:  # noqa: BLE001 - evaluator.py:56-59
+            logger.error(f"Error processing batch {i}: {str(e)}")
+            continue
+    if not preds:
+        logger.error("No valid predictions were made during evaluation.")
+        return None
+    m = lstm_test_metrics(labels_all, preds, probs, class_names, logger)
+    with open(Path(exp_dir) / "test_metrics.json", "w") as f:
+        json.dump(m, f, indent=4)
+    logger.info(f"AUROC: {m['auroc']:.4f}  F1 Score: {m['f1_score']:.4f}  Accuracy: {m['accuracy']:.4f}")
+    logger.info(f"Confusion Matrix:\n{np.asarray(m['confusion_matrix'])}")
+    return m
+
+
+def train_lstm(model, loaders, labels, device, config, exp_dir, logger):
+    """trainer.py:124-398 without wandb and the plots: returns (history, best model path or None)."""
+    from .optim import AdamW
+    exp_dir = Path(exp_dir)
+    pos_weight = torch.tensor([lstm_pos_weight(labels)], dtype=torch.float32, device=device)
+    crit = torch.nn.BCEWithLogitsLoss(pos_weight=pos_weight)
+    # torch.optim.Adam over the trainable parameters (trainer.py:45-48) = AdamW with weight decay 0
+    opt = AdamW([q for q in model.parameters() if q.requires_grad], lr=config["learning_rate"], weight_decay=0.0)
+    sched = torch.optim.lr_scheduler.ReduceLROnPlateau(opt, mode="max", factor=0.5, patience=5)
+    select = LstmModelSelector(config["loss_weight"], config["patience"])
+    logger.info(f"Model selection weights - Loss: {select.loss_weight:.2f}, AUROC: {select.auroc_weight:.2f}")
+    with open(exp_dir / "training_config.json", "w") as f:
+        json.dump({k: str(v) if isinstance(v, Path) else v for k, v in config.items()}, f, indent=4)
+    history = {k: [] for k in LSTM_HISTORY_KEYS}
+    Path(config["model_dir"]).mkdir(parents=True, exist_ok=True)
+    best_path = Path(config["model_dir"]) / f"model_{datetime.now().strftime('%Y%m%d_%H%M%S')}.pth"
+    for epoch in range(config["epochs"]):
+        model.train()
+        tr_loss, tr_acc, tr_auroc, tn = _lstm_epoch(model, loaders["train"], crit, device, opt, logger, "training")
+        model.eval()
+        with torch.no_grad():
+            va_loss, va_acc, va_auroc, vn = _lstm_epoch(model, loaders["val"], crit, device, None, logger, "validation")
+        # a failing batch is logged and skipped, but an epoch in which EVERY batch failed must not go on to
+        # save a "best" model (as run_main)
+        if tn == 0:
+            raise RuntimeError(f"epoch {epoch + 1}: every training batch failed or the train loader is empty (see the log)")
+        if vn == 0:
+            raise RuntimeError(f"epoch {epoch + 1}: every validation batch failed or the val loader is empty (see the log)")
+        sched.step(va_auroc)
+        for k, v in zip(LSTM_HISTORY_KEYS, (tr_loss, va_loss, tr_acc, va_acc, tr_auroc, va_auroc)):
+            history[k].append(float(v))
+        if select.update(va_loss, va_auroc):
+            logger.info(f"Saving best model at epoch {epoch + 1} with val_loss: {va_loss:.4f}, val_auroc: {va_auroc:.4f}")
+            torch.save(model.state_dict(), best_path)
+        else:
+            logger.info(f"Early stopping counter: {select.counter}/{select.patience}")
+            if select.early_stop:
+                logger.info(f"Early stopping triggered at epoch {epoch + 1}")
+                break
+        logger.info(f"Epoch {epoch + 1}/{config['epochs']} - Train Loss: {tr_loss:.4f}, Train Acc: {tr_acc:.4f}, "
+                    f"Train AUROC: {tr_auroc:.4f} | Val Loss: {va_loss:.4f}, Val Acc: {va_acc:.4f}, "
+                    f"Val AUROC: {va_auroc:.4f} | lr {opt.param_groups[0]['lr']:.2e}")
+    if best_path.exists():
+        _lstm_load_state(model, best_path, logger)
+    else:
+        logger.warning("No best model saved, using final model state")
+        best_path = None
+    with open(exp_dir / "training_history.json", "w") as f:
+        json.dump(history, f, indent=4)
+    logger.info(f"Training completed. Best validation results: Loss: {select.best_val_loss:.4f} "
+                f"AUROC: {select.best_val_auroc:.4f}")
+    return history, best_path
+
+
+def run_main_lstm(argv=None):
+    """resnet50-2d-lstm/main.py: returns (test metrics or None, history, experiment dir)."""
+    import os
+    args = build_parser_lstm(inference=False).parse_args(argv)
+    random.seed(LSTM_SEED)  # src/utils/logging_utils.py set_seed(SEED)
+    np.random.seed(LSTM_SEED)
+    torch.manual_seed(LSTM_SEED)
+    Path(args.log_dir).mkdir(parents=True, exist_ok=True)
+    Path(args.model_dir).mkdir(parents=True, exist_ok=True)
+    fam = FAMILIES["lstm"]
+    exp = LstmExperimentLogger(Path(args.log_dir) / f"{fam.prefix}_{datetime.now().strftime('%Y%m%d_%H%M%S')}")
+    logger = exp.get_logger()
+    logger.info("Starting enhanced ResNet50-LSTM training")
+    test_dir = args.test_dir if args.test_dir else args.data_dir
+    config = {k: getattr(args, k) for k in ("data_dir", "model_dir", "train_sampling", "val_sampling", "test_sampling",
+                                            "loss_weight", "learning_rate", "batch_size", "epochs", "patience",
+                                            "hidden_size", "num_layers", "dropout", "sequence_length")}
+    config.update(test_dir=test_dir, log_dir=exp.get_experiment_dir())
+    device = _device()
+    logger.info(f"Using device: {device}")
+    from .data_config import lstm as data
+    from .resnet50_lstm import create_model
+    use_ckpt = bool(args.checkpoint_path and os.path.isfile(args.checkpoint_path))
+    train = not use_ckpt and not args.skip_train  # main.py:180-199
+    datasets, loaders = data.create_dataloaders(args, logger, splits=("train", "val", "test") if train else ("test",))
+    logger.info(f"Using training/validation data from: {args.data_dir}")
+    logger.info(f"Using test data from: {test_dir}")
+    model = create_model(args.hidden_size, args.num_layers, args.dropout, device=device)
+    history = {k: [] for k in LSTM_HISTORY_KEYS}
+    if use_ckpt:
+        logger.info(f"Loading checkpoint from {args.checkpoint_path}")
+        _lstm_load_state(model, args.checkpoint_path, logger)
+        best_path = args.checkpoint_path
+    elif train:
+        history, best_path = train_lstm(model, loaders, datasets["train"].labels, device, config,
+                                        exp.get_experiment_dir(), logger)
+        logger.info(f"Training completed. Best model saved to {best_path}")
+    else:
+        logger.info("Skipping training as requested")
+        best_path = None
+    if not best_path:
+        logger.error("No model available for evaluation")
+        return None, history, exp.get_experiment_dir()
+    logger.info(f"Evaluating model from {best_path}")
+    m = evaluate_lstm(model, loaders["test"], device, exp.get_experiment_dir(), logger, LSTM_CLASS_NAMES)
+    return m, history, exp.get_experiment_dir()
+
+
+def lstm_inference_videos(args):
+    """inference.py:250-267: the three ways the reference lists its videos; besides its extensions the
+    formats vclip_amd.video_io decodes (`.npy` clips)."""
+    import glob
+    import os
+    if args.single_video:
+        return [args.single_video] if os.path.exists(args.single_video) else None
+    files = []
+    if args.batch_mode:
+        for ext in ("*.mp4", "*.avi", "*.mov", "*.npy"):
+            files.extend(glob.glob(os.path.join(args.videos_dir, "**", ext), recursive=True))
+    else:
+        for dir_name in ("referral", "non_referral"):
+            for ext in ("*.mp4", "*.npy"):
+                files.extend(glob.glob(os.path.join(args.videos_dir, dir_name, ext)))
+    return files
+
+
+LSTM_INFERENCE_SAMPLERS = {"random": sampling.lstm_random_sampling, "random_window": sampling.lstm_random_window_sampling,
+                           "uniform": sampling.lstm_uniform_sampling}
+
+
+def lstm_model_from_checkpoint(path, device):
+    """VideoResNet50LSTM of the checkpoint's own LSTM shape (the reference's inference script builds
+    DEFAULT_CONFIG's 256 x 2, which a checkpoint trained with other --hidden_size / --num_layers cannot load)."""
+    from .resnet50_lstm import VideoResNet50LSTM
+    sd = torch.load(path, map_location="cpu", weights_only=True)
+    sd = {k[len("module."):] if k.startswith("module.") else k: v for k, v in sd.items()}
+    hidden = int(sd["lstm.weight_hh_l0"].shape[1])
+    layers = sum(1 for k in sd if k.startswith("lstm.weight_hh_l"))
+    model = VideoResNet50LSTM(hidden, layers, 0.5)
+    model.load_state_dict(sd)
+    return model.to(device).eval()
+
+
+def _lstm_load_video(path, method, sequence_length, device):
+    """inference.py:132-178 up to the model: (clip f32 [1, 3, T, 224, 224], frame indices, total frames) with
+    T = min(sequence_length, total frames)."""
+    from . import preprocess as pp
+    src = video_io.open_video(path)
+    total = src.total_frames
+    idx = [int(i) for i in LSTM_INFERENCE_SAMPLERS.get(method, sampling.lstm_uniform_sampling)(total, sequence_length)]
+    frames = torch.from_numpy(np.ascontiguousarray(src.read(idx))).to(device)
+    frames = pp.cv2_resize_u8(frames, (224, 224))
+    return pp.lstm_inference_preprocess(frames), idx, total
+
+
+def _write_csv(rows, path):
+    """pd.DataFrame(rows).to_csv(path, index=False) (inference.py:310-321); the csv module where pandas is absent."""
+    try:
+        import pandas as pd
+    except ImportError:
+        import csv
+        with open(path, "w", newline="") as f:
+            w = csv.DictWriter(f, fieldnames=list(rows[0].keys()))
+            w.writeheader()
+            w.writerows(rows)
+        return
+    pd.DataFrame(rows).to_csv(path, index=False)
+
+
+def run_inference_lstm(argv=None):
+    """resnet50-2d-lstm/inference.py on batched ragged inference: up to --videos_per_batch videos, each with
+    its own (clamped) frame count, go through one `forward_ragged`.  Returns the summary dict (None when no
+    video was found or none succeeded), with the experiment directory under "output_dir"."""
+    import os
+    args = build_parser_lstm(inference=True).parse_args(argv)
+    exp = LstmExperimentLogger(os.path.join(args.output_dir, f"inference_{datetime.now().strftime('%Y%m%d_%H%M%S')}"),
+                               prefix="inference")
+    logger = exp.get_logger()
+    out_dir = exp.get_experiment_dir()
+    if args.visualize:
+        logger.warning("--visualize: plots are not part of this build; the CSV / JSON results are written as usual")
+    if args.videos_per_batch < 1:
+        raise ValueError("--videos_per_batch must be >= 1")
+    device = _device()
+    model = lstm_model_from_checkpoint(args.model_path, device)
+    video_files = lstm_inference_videos(args)
+    if video_files is None:
+        logger.error(f"Video file not found: {args.single_video}")
+        return None
+    if not video_files:
+        logger.error("No video files found to process")
+        return None
+    logger.info(f"Found {len(video_files)} videos to process")
+    results = [None] * len(video_files)
+
+    def error_row(path, e):
+        print(f"Error processing video {path}: {str(e)}")
+        return {"video_path": path, "prediction": None, "probability": None, "status": f"error: {str(e)}"}
+
+    def flush(batch):
+        if not batch:
+            return
+        try:
+            with torch.no_grad():
+                logits = model.forward_ragged(torch.cat([c for _, c, _, _ in batch], dim=2), [len(i) for _, _, i, _ in batch])
+            probs = torch.sigmoid(logits.float()).reshape(-1).tolist()
+        except Exception as e:  # noqa: BLE001 - the whole call failed: its videos get the error row
+            for k, _, _, _ in batch:
+                results[k] = error_row(video_files[k], e)
+            return
+        for (k, _, idx, total), p in zip(batch, probs):
+            results[k] = {"video_path": video_files[k], "prediction": "referral" if p >= 0.5 else "non_referral",
+                          "probability": float(p), "sampled_frames": len(idx), "total_frames": total,
+                          "frame_indices": idx, "status": "success"}
+
+    batch = []
+    for k, path in enumerate(video_files):
+        try:  # a video that fails to open or decode does not take its batch down (inference.py:196-203)
+            clip, idx, total = _lstm_load_video(path, args.sampling_method, args.sequence_length, device)
+        except Exception as e:  # noqa: BLE001
+            results[k] = error_row(path, e)
+            continue
+        batch.append((k, clip, idx, total))
+        if len(batch) == args.videos_per_batch:
+            flush(batch)
+            batch = []
+    flush(batch)
+    for r in results:
+        name = os.path.basename(r["video_path"])
+        if r["status"] == "success":
+            conf = r["probability"] if r["prediction"] == "referral" else 1 - r["probability"]
+            logger.info(f"Video: {name}, Prediction: {r['prediction']}, Confidence: {conf:.4f}")
+        else:
+            logger.error(f"Error processing {name}: {r['status']}")
+    ok = [r for r in results if r["status"] == "success"]
+    failed = [r for r in results if r["status"] != "success"]
+    if not ok:
+        logger.error("No successful predictions were made")
+        return None
+    summary = {"total_videos": len(results), "successful_predictions": len(ok), "failed_predictions": len(failed),
+               "referral_cases": sum(1 for r in ok if r["prediction"] == "referral"),
+               "non_referral_cases": sum(1 for r in ok if r["prediction"] == "non_referral"),
+               "sampling_method": args.sampling_method, "sequence_length": args.sequence_length,
+               "model_path": args.model_path}
+    _write_csv(ok, out_dir / "inference_results.csv")
+    if failed:
+        _write_csv(failed, out_dir / "inference_failures.csv")
+    with open(out_dir / "inference_summary.json", "w") as f:
+        json.dump(summary, f, indent=4)
+    _write_csv([summary], out_dir / "inference_summary.csv")
+    logger.info(f"Total videos processed: {len(results)}  successful: {len(ok)}  failed: {len(failed)}  "
+                f"referral: {summary['referral_cases']}  non-referral: {summary['non_referral_cases']}")
+    logger.info(f"Results saved to {out_dir}")
+    return dict(summary, output_dir=str(out_dir))

@@ -191,6 +191,120 @@ lstm_seq_fwd_kernel(const float* __restrict__ pre, int64_t ldpre, int B, int T, 
     }
 }
 
+// The inference recurrence over sequences of different lengths: sequence b owns rows row0[b] ..
+// row0[b] + len[b] - 1 of pre and hseq.  Same schedule, slice-order reduction and cell arithmetic as
+// lstm_seq_fwd_kernel, so every sequence comes out bit-identical to a dense launch on it alone (the
+// lanes of a packed FMA are independent).  The workgroup loops to the largest length of its group
+// (uniform: the barriers stay legal); a sequence past its end keeps its h in LDS untouched, reads no
+// row of pre and writes nothing.  hlast[b] = h of step len[b] - 1, zero for len[b] = 0.
+template <int G>
+__global__ void __launch_bounds__(kMaxThreads)
+lstm_seq_fwd_ragged_kernel(const float* __restrict__ pre, int64_t ldpre, int B, const int32_t* __restrict__ row0,
+                           const int32_t* __restrict__ len, int max_len, int H, const float* __restrict__ WT,
+                           uint16_t* __restrict__ hseq, int64_t ldh, float* __restrict__ hlast) {
+    extern __shared__ __align__(16) float smem[];
+    const int HP = (H + 63) & ~63;
+    const int S = kMaxThreads / HP;
+    const int j = threadIdx.x % HP, s = threadIdx.x / HP;
+    float* hl = smem;                      // [H][G]   h_{t-1} of the group
+    float* part = smem + (size_t)H * G;    // [S - 1][4 * G][HP] partial gate sums of slices 1 .. S-1
+    const int b0 = blockIdx.x * G;
+    const int nb = min(G, B - b0);
+    const int KC = (H + S - 1) / S;
+    const int k0 = s * KC, k1 = min(H, k0 + KC);
+    const bool unit = j < H;
+    const int64_t H4 = 4 * (int64_t)H;
+
+    int r0[G], ln[G];  // uniform over the workgroup
+    int T = 0;
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+        r0[g] = g < nb ? row0[b0 + g] : 0;
+        ln[g] = g < nb ? min(max(len[b0 + g], 0), max_len) : 0;
+        T = max(T, ln[g]);
+    }
+
+    float c[G];
+#pragma unroll
+    for (int g = 0; g < G; ++g) c[g] = 0.f;
+    for (int i = threadIdx.x; i < H * G; i += blockDim.x) hl[i] = 0.f;
+    if (s == 0 && unit) {
+#pragma unroll
+        for (int g = 0; g < G; ++g)
+            if (g < nb && ln[g] == 0) hlast[(int64_t)(b0 + g) * H + j] = 0.f;
+    }
+    __syncthreads();
+
+    for (int t = 0; t < T; ++t) {
+        v2f acc[4][G / 2];
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+#pragma unroll
+            for (int p = 0; p < G / 2; ++p) acc[q][p] = v2f{0.f, 0.f};
+        if (t > 0 && unit) {  // h_{-1} = 0
+            const float* w = WT + (int64_t)k0 * H4 + j;
+#pragma unroll 2
+            for (int k = k0; k < k1; ++k, w += H4) {
+                const float w0 = w[0], w1 = w[H], w2 = w[2 * (int64_t)H], w3 = w[3 * (int64_t)H];
+                const v2f* hv = reinterpret_cast<const v2f*>(hl + (size_t)k * G);
+#pragma unroll
+                for (int p = 0; p < G / 2; ++p) {
+                    const v2f h2 = hv[p];
+                    acc[0][p] += h2 * w0;
+                    acc[1][p] += h2 * w1;
+                    acc[2][p] += h2 * w2;
+                    acc[3][p] += h2 * w3;
+                }
+            }
+        }
+        if (s > 0) {
+            float* pp = part + (size_t)(s - 1) * 4 * G * HP + j;
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+#pragma unroll
+                for (int p = 0; p < G / 2; ++p) {
+                    pp[(size_t)(q * G + 2 * p) * HP] = acc[q][p].x;
+                    pp[(size_t)(q * G + 2 * p + 1) * HP] = acc[q][p].y;
+                }
+        }
+        __syncthreads();  // partials written; every read of h_{t-1} done
+        if (s == 0 && unit) {
+#pragma unroll 1
+            for (int r = 1; r < S; ++r) {
+                const float* pp = part + (size_t)(r - 1) * 4 * G * HP + j;
+#pragma unroll
+                for (int q = 0; q < 4; ++q)
+#pragma unroll
+                    for (int p = 0; p < G / 2; ++p) {
+                        acc[q][p].x += pp[(size_t)(q * G + 2 * p) * HP];
+                        acc[q][p].y += pp[(size_t)(q * G + 2 * p + 1) * HP];
+                    }
+            }
+#pragma unroll
+            for (int g = 0; g < G; ++g) {
+                if (t >= ln[g]) {  // past this sequence's end (ln = 0 for absent sequences)
+                    continue;
+                }
+                const int64_t row = (int64_t)r0[g] + t;
+                const float* pr = pre + row * ldpre + j;
+                const float a_i = pr[0] + ((g & 1) ? acc[0][g / 2].y : acc[0][g / 2].x);
+                const float a_f = pr[H] + ((g & 1) ? acc[1][g / 2].y : acc[1][g / 2].x);
+                const float a_g = pr[2 * (int64_t)H] + ((g & 1) ? acc[2][g / 2].y : acc[2][g / 2].x);
+                const float a_o = pr[3 * (int64_t)H] + ((g & 1) ? acc[3][g / 2].y : acc[3][g / 2].x);
+                const float ig = sigmoidf_(a_i), fg = sigmoidf_(a_f), gg = tanhf_(a_g), og = sigmoidf_(a_o);
+                // the dense kernel's contraction of fg * c + ig * gg, spelled out: left to the compiler, this
+                // kernel got one packed multiply of both products and an unfused add (a last-bit difference)
+                c[g] = __builtin_fmaf(fg, c[g], ig * gg);
+                const float hn = og * tanhf_(c[g]);
+                hl[(size_t)j * G + g] = hn;
+                hseq[row * ldh + j] = f2bf(hn);
+                if (t == ln[g] - 1) hlast[(int64_t)(b0 + g) * H + j] = hn;
+            }
+        }
+        __syncthreads();  // h_t visible; partials consumed
+    }
+}
+
 // BPTT, t = T-1 .. 0, from the saved gates and c.  dh: last_only = 0: [B*T][H] rows b*T + t;
 // last_only = 1: [B][H], the gradient of the last step's h only.  keep (optional) scales the incoming
 // dh rows like the forward scaled the stored h_seq.  W = W_hh [4H][H].  Writes dpre fp32 and bf16.
@@ -460,6 +574,28 @@ int vc_lstm_seq_fwd(const float* pre, int64_t ldpre, int64_t B, int64_t T, int64
         lstm_seq_fwd_kernel<2><<<grid, block, lds, stream>>>(pre, ldpre, (int)B, (int)T, H, W_hh_t, keep, h_seq, ldh, h_last,
                                                              gates, c_seq, h_prev, ldhp);
     return check_launch("vc_lstm_seq_fwd");
+}
+
+int vc_lstm_seq_fwd_ragged(const float* pre, int64_t ldpre, int64_t B, const int32_t* row0, const int32_t* len,
+                           int64_t max_len, int64_t hidden, const float* W_hh_t, uint16_t* h_seq, int64_t ldh,
+                           float* h_last, hipStream_t stream) {
+    if (!pre || !row0 || !len || !W_hh_t || !h_seq || !h_last)
+        return fail(VC_ERR_INVALID_ARG, "vc_lstm_seq_fwd_ragged: null pointer");
+    if (const char* m = check_hidden(B, max_len, hidden))
+        return fail(VC_ERR_INVALID_ARG, std::string("vc_lstm_seq_fwd_ragged (T = max_len): ") + m);
+    if (ldpre < 4 * hidden || ldh < hidden)
+        return fail(VC_ERR_INVALID_ARG, "vc_lstm_seq_fwd_ragged: row stride below the row length");
+    const int H = (int)hidden, G = group_of(hidden);
+    const int HP = (H + 63) & ~63, S = kMaxThreads / HP;
+    const size_t lds = ((size_t)H * G + (size_t)(S - 1) * 4 * G * HP) * sizeof(float);
+    const unsigned grid = (unsigned)((B + G - 1) / G), block = (unsigned)(S * HP);
+    if (G == 4)
+        lstm_seq_fwd_ragged_kernel<4><<<grid, block, lds, stream>>>(pre, ldpre, (int)B, row0, len, (int)max_len, H, W_hh_t,
+                                                                    h_seq, ldh, h_last);
+    else
+        lstm_seq_fwd_ragged_kernel<2><<<grid, block, lds, stream>>>(pre, ldpre, (int)B, row0, len, (int)max_len, H, W_hh_t,
+                                                                    h_seq, ldh, h_last);
+    return check_launch("vc_lstm_seq_fwd_ragged");
 }
 
 int vc_lstm_seq_bwd(const float* gates, const float* c_seq, int64_t B, int64_t T, int64_t hidden, const float* W_hh,

@@ -6,8 +6,11 @@ formats:
   vclip_amd.data_config.timesformer  timesformer/timesformer_classifier/data_config/
   vclip_amd.data_config.swin         videoswintransformer/swin_video_classifier/data_config/
   vclip_amd.data_config.resnet3d     resnet50-3d-video/video_classifier/data_config/
+  vclip_amd.data_config.lstm         resnet50-2d-lstm/src/data_config/ (`VideoDataset(root_dir, split,
+                                     sampling_method, sequence_length, transform, logger)`; the loaders of
+                                     its main.py as `create_dataloaders`; no collate function, as there)
 
-each exporting `VideoDataset`, `video_collate_fn` and `create_dataloaders` with the reference's signature.
+the first four exporting `VideoDataset`, `video_collate_fn` and `create_dataloaders` with the reference's signature.
 
 Where the work runs: sampling (bit-exact, vclip_amd.sampling) and decode are host work in the
 DataLoader's worker processes (`num_workers`), as in the reference.  The Swin3D / ResNet3D datasets
@@ -19,9 +22,9 @@ collates exactly as the reference collate does.  Indexing such a dataset directl
 (`ds[i]`) runs both halves and returns the reference item.  ViViT / TimeSformer items are the decoded
 uint8 frames themselves (their processors run in the trainer, on the GPU in this build).
 """
-from . import resnet3d, swin, timesformer, vivit
+from . import lstm, resnet3d, swin, timesformer, vivit
 from ._device import DeviceClipLoader
 
-FOLDERS = {"vivit": vivit, "timesformer": timesformer, "swin": swin, "resnet3d": resnet3d}
+FOLDERS = {"vivit": vivit, "timesformer": timesformer, "swin": swin, "resnet3d": resnet3d, "lstm": lstm}
 
-__all__ = ["FOLDERS", "DeviceClipLoader", "vivit", "timesformer", "swin", "resnet3d"]
+__all__ = ["FOLDERS", "DeviceClipLoader", "vivit", "timesformer", "swin", "resnet3d", "lstm"]

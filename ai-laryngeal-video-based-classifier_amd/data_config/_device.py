@@ -30,13 +30,14 @@ class DeviceClipLoader:
     the GPU by `dataset.transform_span` and the batch is collated by `collate` (the folder's
     `video_collate_fn`, or torch's default collate where the reference passes none)."""
 
-    def __init__(self, dataset, batch_size=1, shuffle=False, num_workers=0, collate_fn=None, pin_memory=False):
+    def __init__(self, dataset, batch_size=1, shuffle=False, num_workers=0, collate_fn=None, pin_memory=False,
+                 drop_last=False):
         self.dataset = dataset
         self.batch_size = batch_size
         self.num_workers = num_workers
         self.collate_fn = collate_fn or torch.utils.data.default_collate
         self.loader = DataLoader(_HostSpans(dataset), batch_size=batch_size, shuffle=shuffle,
-                                 num_workers=num_workers, collate_fn=_as_batch)
+                                 num_workers=num_workers, collate_fn=_as_batch, drop_last=drop_last)
 
     def __len__(self):
         return len(self.loader)

@@ -1070,6 +1070,65 @@ def lstm_seq_fwd(pre: torch.Tensor, B: int, T: int, hidden: int, w_hh_t: torch.T
     return h_last
 
 
+_RAGGED_TABLES = {}  # (lengths, row0, device) -> (row0 int32 [B], len int32 [B]) on the device
+
+
+def _ragged_tables(lengths: tuple, row0: tuple, device) -> tuple:
+    key = (lengths, row0, str(device))
+    tab = _RAGGED_TABLES.get(key)
+    if tab is None:
+        if len(_RAGGED_TABLES) >= 256:  # a directory of videos has few distinct batches; do not grow without bound
+            _RAGGED_TABLES.clear()
+        tab = (torch.tensor(row0, dtype=torch.int32, device=device), torch.tensor(lengths, dtype=torch.int32, device=device))
+        _RAGGED_TABLES[key] = tab
+    return tab
+
+
+def lstm_seq_fwd_ragged(pre: torch.Tensor, lengths, hidden: int, w_hh_t: torch.Tensor, h_seq: torch.Tensor,
+                        h_last: torch.Tensor, row0=None) -> torch.Tensor:
+    """The inference recurrence over len(lengths) sequences of different lengths: sequence b owns rows
+    row0[b] .. row0[b] + lengths[b] - 1 of pre f32 [rows, 4H] and h_seq bf16 [rows, H] (row0 defaults to the
+    exclusive prefix sum of lengths: the sequences back to back); h_last f32 [B, H] = h of each sequence's
+    last step.  Each sequence's rows are bit-identical to lstm_seq_fwd on it alone.  lengths and row0 are
+    host integers, lengths >= 1; their device copies are cached per (lengths, row0, device)."""
+    lengths = tuple(int(n) for n in lengths)
+    B = len(lengths)
+    _need(B >= 1 and all(n >= 1 for n in lengths), "lstm_seq_fwd_ragged: lengths must be a non-empty sequence of ints >= 1")
+    _lstm_shape(B, max(lengths), hidden)
+    if row0 is None:
+        acc, r = 0, []
+        for n in lengths:
+            r.append(acc)
+            acc += n
+        row0 = tuple(r)
+    else:
+        row0 = tuple(int(r) for r in row0)
+        _need(len(row0) == B and all(r >= 0 for r in row0), "lstm_seq_fwd_ragged: row0 must hold one row index >= 0 per sequence")
+    _dev(pre, w_hh_t, h_seq, h_last)
+    _need(pre.dtype == torch.float32 and pre.dim() == 2 and pre.shape[1] >= 4 * hidden and pre.stride(1) == 1,
+          "lstm_seq_fwd_ragged: pre f32 [rows, >= 4H]")
+    _need(w_hh_t.dtype == torch.float32 and w_hh_t.is_contiguous() and tuple(w_hh_t.shape) == (hidden, 4 * hidden),
+          "lstm_seq_fwd_ragged: w_hh_t f32 contiguous [H, 4H] (weight_hh transposed)")
+    _need(h_seq.dtype == torch.bfloat16 and h_seq.dim() == 2 and h_seq.shape[1] >= hidden and h_seq.stride(1) == 1,
+          "lstm_seq_fwd_ragged: h_seq bf16 [rows, >= H]")
+    _need(h_last.dtype == torch.float32 and h_last.is_contiguous() and h_last.numel() >= B * hidden,
+          "lstm_seq_fwd_ragged: h_last f32 [B, H]")
+    rows = min(pre.shape[0], h_seq.shape[0])
+    _need(all(r + n <= rows for r, n in zip(row0, lengths)) and rows < 2 ** 31,
+          f"lstm_seq_fwd_ragged: a sequence runs past the {rows} rows of pre / h_seq")
+    end = 0
+    for r, n in sorted(zip(row0, lengths)):
+        _need(r >= end, "lstm_seq_fwd_ragged: two sequences overlap")
+        end = r + n
+    d_row0, d_len = _ragged_tables(lengths, row0, pre.device)
+    G = lstm_group(hidden)
+    steps = sum(max(lengths[i:i + G]) for i in range(0, B, G))  # W_hh is streamed once per step and group
+    timed("lstm_seq_fwd_ragged_kernel", "lstm_fwd", 4.0 * hidden * hidden * 4 * steps, "byte", _lib.call,
+          "vc_lstm_seq_fwd_ragged", _p(pre), pre.stride(0), B, _p(d_row0), _p(d_len), max(lengths), hidden, _p(w_hh_t),
+          _p(h_seq), h_seq.stride(0), _p(h_last), _stream(pre))
+    return h_last
+
+
 def lstm_seq_bwd(gates: torch.Tensor, c_seq: torch.Tensor, B: int, T: int, hidden: int, w_hh: torch.Tensor,
                  dh: torch.Tensor, dpre: torch.Tensor, dpre_bf16: torch.Tensor, last_only: bool = False,
                  keep: torch.Tensor | None = None) -> torch.Tensor:

@@ -238,6 +238,18 @@ def video_train_transform(frames: torch.Tensor, num_frames: int, min_size: int =
     return out, params
 
 
+def lstm_inference_preprocess(frames: torch.Tensor, mean=(0.45, 0.45, 0.45), std=(0.225, 0.225, 0.225)) -> torch.Tensor:
+    """frames u8 [T, H, W, 3] (device, already resized) -> clip f32 [1, 3, T, H, W] = (x/255 - mean)/std
+    (resnet50-2d-lstm/inference.py:165-178)."""
+    _dev(frames)
+    _need(frames.dim() == 4, "lstm_inference_preprocess: frames u8 [T, H, W, 3]")
+    T, H, W, C = frames.shape
+    idx = torch.arange(T, device=frames.device, dtype=torch.int64).reshape(1, T).contiguous()
+    scale = tuple(1.0 / (255.0 * s) for s in std)
+    shift = tuple(-m / s for m, s in zip(mean, std))
+    return _transform(frames.contiguous().unsqueeze(0), idx, T, (H, W), (0, 0, H, W), scale, shift, layout=1)
+
+
 def timesformer_preprocess(frames: torch.Tensor, mean=(0.45, 0.45, 0.45), std=(0.225, 0.225, 0.225)) -> torch.Tensor:
     """frames u8 [B, T, 224, 224, 3] -> pixel_values f32 [B, T, 3, 224, 224] = (x/255 - mean)/std."""
     _dev(frames)

@@ -140,6 +140,17 @@ class VideoResNet50LSTM(torch.nn.Module):
                                   hlast=z(B, self.hidden, torch.float32), logits=z(B, 1, torch.float32))}
         return self._ws[key]
 
+    def _workspace_ragged(self, N, B, device):
+        """forward_ragged's buffers: N frame rows in all, B sequences; one (N, B) at a time, like _workspace."""
+        key = ("ragged", N, B, str(device))
+        if key not in self._ws:
+            M = _ru(N, 256)
+            z = lambda r, c, dt: torch.zeros(r, c, dtype=dt, device=device)  # noqa: E731
+            self._ws = {key: dict(pre=z(M, _ru(4 * self.hidden, 128), torch.float32),
+                                  hseq=[z(M, _ru(self.hidden, 128), torch.bfloat16) for _ in range(2)],
+                                  hlast=z(B, self.hidden, torch.float32), logits=z(B, 1, torch.float32))}
+        return self._ws[key]
+
     # ---- forward -----------------------------------------------------------------------
     def forward(self, video: torch.Tensor) -> torch.Tensor:
         """`model(video)` -> logits f32 [B, 1].  In training mode the train step runs (batch-statistic
@@ -275,6 +286,35 @@ class VideoResNet50LSTM(torch.nn.Module):
             inp = ws["hseq"][l & 1]
         w1, b1, w2, b2 = pk["head"]
         return ops.mlp_head_fwd(ws["hlast"], w1, b1, w2, b2, ws["logits"])
+
+    def forward_ragged(self, video: torch.Tensor, lengths) -> torch.Tensor:
+        """Batched inference over videos of different lengths: `video` f32 [1, 3, N, H, W] holds the frames of
+        len(lengths) videos back to back (N == sum(lengths), every length >= 1) -> logits f32
+        [len(lengths), 1], row b for the frames of video b.  The frames are independent through the
+        backbone (every kernel is kt = 1), so it runs once over the N frames; each LSTM layer is one
+        input-projection GEMM over the N rows and one ragged recurrence (vc_lstm_seq_fwd_ragged).  Eval mode
+        only: the train step's batch-statistic BatchNorm would mix the videos."""
+        if self.training:
+            raise RuntimeError("forward_ragged is the inference path: call model.eval() first")
+        if not isinstance(video, torch.Tensor) or video.device.type != "cuda":
+            raise RuntimeError("VideoResNet50LSTM (vclip_amd) runs on the GPU only: move the clip batch to cuda")
+        lengths = tuple(int(n) for n in lengths)
+        if video.dim() != 5 or video.shape[0] != 1 or video.shape[1] != 3:
+            raise ValueError("video must be [1, 3, N, H, W]: the frames of all videos back to back")
+        if not lengths or min(lengths) < 1 or sum(lengths) != video.shape[2]:
+            raise ValueError(f"lengths {lengths} must be >= 1 and sum to the {video.shape[2]} frames of video")
+        x = video.contiguous().float() if video.dtype != torch.float32 else video.contiguous()
+        N, B = x.shape[2], len(lengths)
+        with torch.no_grad():
+            pk = self._pack(x.device)
+            ws = self._workspace_ragged(N, B, x.device)
+            inp = self.features(x)
+            for l, L in enumerate(pk["layers"]):
+                ops.gemm(inp, L["wb"], L["b"], "bias_f32", ws["pre"], op="lstm_ih")
+                ops.lstm_seq_fwd_ragged(ws["pre"], lengths, self.hidden, L["w_hh_t"], ws["hseq"][l & 1], ws["hlast"])
+                inp = ws["hseq"][l & 1]
+            w1, b1, w2, b2 = pk["head"]
+            return ops.mlp_head_fwd(ws["hlast"], w1, b1, w2, b2, ws["logits"]).clone()
 
     def _forward_train(self, video: torch.Tensor) -> torch.Tensor:
         B, _, T = video.shape[:3]

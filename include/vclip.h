@@ -693,6 +693,23 @@ int vc_lstm_seq_fwd(const float* pre, int64_t ldpre, int64_t B, int64_t T, int64
                     uint16_t* h_prev, int64_t ldhp, hipStream_t stream);
 
 /*
+ * The inference recurrence over B sequences of different lengths in one launch (batched inference
+ * over videos shorter than the requested frame count).
+ *   row0, len  device int32 [B]: sequence b owns rows row0[b] .. row0[b] + len[b] - 1 of pre and h_seq
+ *              (the caller guarantees they lie inside both buffers and do not overlap);
+ *   max_len    the host's upper bound on len; the kernel clamps every length to [0, max_len].
+ * A workgroup owns 4 sequences (2 for hidden > 512) as in vc_lstm_seq_fwd and runs to the largest
+ * length of its group; a sequence past its end reads no row of pre and writes nothing.
+ * h_last[b] = the unmasked h of step len[b] - 1; a sequence of length 0 gets a zero h_last row and
+ * nothing else.  Every sequence's h_seq rows and h_last row are bit-identical to vc_lstm_seq_fwd
+ * (inference variant, keep = NULL) run on that sequence alone.  Deterministic, no atomics.
+ * hidden % 4 == 0, hidden <= 1024; B, max_len >= 1.
+ */
+int vc_lstm_seq_fwd_ragged(const float* pre, int64_t ldpre, int64_t B, const int32_t* row0, const int32_t* len,
+                           int64_t max_len, int64_t hidden, const float* W_hh_t, uint16_t* h_seq, int64_t ldh,
+                           float* h_last, hipStream_t stream);
+
+/*
  * Its backward through time, t = T-1 .. 0 in one launch, from the saved gates and c_seq.
  *   W_hh    f32 [4*hidden][hidden], natural layout;
  *   dh      last_only = 0: f32 [B*T][hidden] (row b*T + t, stride lddh), dL/d(h_seq);
