@@ -3,7 +3,11 @@
 // (the input projections of all T steps run outside as MFMA GEMMs, the weight gradients as the
 // split-K wgrad GEMMs) and the Linear -> ReLU -> Dropout -> Linear head, forward and backward.
 //
-// The two recurrence kernels share one schedule.  A workgroup owns G whole sequences (G = 4 for
+// There are two recurrence kernels, one forward and one backward.  The forward one is a template over
+// <G, RAGGED>: dense inference, dense train (gates != nullptr) and the ragged inference over
+// sequences of different lengths are instantiations of one step loop, so a sequence comes out
+// bit-identical whichever entry ran it.  Both kernels share one schedule, whose launch geometry the
+// host keeps in SeqLaunch.  A workgroup owns G whole sequences (G = 4 for
 // hidden <= 512, else 2) from the first step to the last, so there is no cross-workgroup barrier.
 // HP = hidden rounded up to 64; the block has S * HP threads, S = 1024 / HP.  Thread (s, j) owns
 // hidden unit j and slice s of the reduction (forward: the k range of h_{t-1}; backward: the row
@@ -85,13 +89,23 @@ __global__ void __launch_bounds__(256) video_to_cl_h16_kernel(const float* __res
 }
 
 // One launch = all T steps of one layer.  pre[b*T + t][4H] = x_t W_ih^T + b_ih + b_hh (gate order
-// i, f, g, o); WT = W_hh^T [H][4H].  Train outputs (gates != nullptr): post-activation gates, c, and
-// bf16 h_{t-1} (zero at t = 0).  keep (optional, [B*T][H]) scales the stored h_seq only.
-template <int G>
+// i, f, g, o); WT = W_hh^T [H][4H].  Sequence b0 + g of the group owns rows r0[g] .. r0[g] + ln[g] - 1
+// of pre and hseq; hlast[b] = h of its last step.
+// Dense (RAGGED = false): r0 = b * T and ln = T in registers, row0 / len are not read.  Train outputs
+// (gates != nullptr): post-activation gates, c, and bf16 h_{t-1} (zero at t = 0).  keep (optional,
+// [B*T][H]) scales the stored h_seq only.
+// Ragged (RAGGED = true, inference only): r0 = row0[b], ln = len[b] clamped to [0, T = max_len]; keep,
+// gates, cseq and hprev are not touched.  The workgroup loops to the largest length of its group
+// (uniform: the barriers stay legal); a sequence past its end keeps its h in LDS untouched, reads no
+// row of pre and writes nothing; hlast[b] = 0 for len[b] = 0.  The step loop is the dense one and
+// the lanes of a packed FMA are independent, so every sequence comes out bit-identical to a dense
+// launch on it alone.
+template <int G, bool RAGGED>
 __global__ void __launch_bounds__(kMaxThreads)
 lstm_seq_fwd_kernel(const float* __restrict__ pre, int64_t ldpre, int B, int T, int H, const float* __restrict__ WT,
-                    const float* __restrict__ keep, uint16_t* __restrict__ hseq, int64_t ldh, float* __restrict__ hlast,
-                    float* __restrict__ gates, float* __restrict__ cseq, uint16_t* __restrict__ hprev, int64_t ldhp) {
+                    const int32_t* __restrict__ row0, const int32_t* __restrict__ len, const float* __restrict__ keep,
+                    uint16_t* __restrict__ hseq, int64_t ldh, float* __restrict__ hlast, float* __restrict__ gates,
+                    float* __restrict__ cseq, uint16_t* __restrict__ hprev, int64_t ldhp) {
     extern __shared__ __align__(16) float smem[];
     const int HP = (H + 63) & ~63;
     const int S = kMaxThreads / HP;
@@ -105,13 +119,35 @@ lstm_seq_fwd_kernel(const float* __restrict__ pre, int64_t ldpre, int B, int T, 
     const bool unit = j < H;
     const int64_t H4 = 4 * (int64_t)H;
 
+    int64_t r0[G];  // uniform over the workgroup, like ln and steps
+    int ln[G];      // 0 for the absent sequences of a partial group
+    int steps = 0;
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+        if constexpr (RAGGED) {
+            r0[g] = g < nb ? row0[b0 + g] : 0;
+            ln[g] = g < nb ? min(max(len[b0 + g], 0), T) : 0;
+        } else {
+            r0[g] = (int64_t)(b0 + g) * T;
+            ln[g] = g < nb ? T : 0;
+        }
+        steps = max(steps, ln[g]);
+    }
+
     float c[G];
 #pragma unroll
     for (int g = 0; g < G; ++g) c[g] = 0.f;
     for (int i = threadIdx.x; i < H * G; i += blockDim.x) hl[i] = 0.f;
+    if constexpr (RAGGED) {
+        if (s == 0 && unit) {
+#pragma unroll
+            for (int g = 0; g < G; ++g)
+                if (g < nb && ln[g] == 0) hlast[(int64_t)(b0 + g) * H + j] = 0.f;
+        }
+    }
     __syncthreads();
 
-    for (int t = 0; t < T; ++t) {
+    for (int t = 0; t < steps; ++t) {
         // acc[gate][pair] = sum over this slice's k of W_hh[gate*H + j][k] * h_{t-1}[k]
         v2f acc[4][G / 2];
 #pragma unroll
@@ -159,10 +195,10 @@ lstm_seq_fwd_kernel(const float* __restrict__ pre, int64_t ldpre, int B, int T, 
             }
 #pragma unroll
             for (int g = 0; g < G; ++g) {
-                if (g >= nb) {
+                if (t >= ln[g]) {  // past this sequence's end, or an absent sequence
                     continue;
                 }
-                const int64_t row = (int64_t)(b0 + g) * T + t;
+                const int64_t row = r0[g] + t;
                 const float* pr = pre + row * ldpre + j;
                 const float a_i = pr[0] + ((g & 1) ? acc[0][g / 2].y : acc[0][g / 2].x);
                 const float a_f = pr[H] + ((g & 1) ? acc[1][g / 2].y : acc[1][g / 2].x);
@@ -170,135 +206,25 @@ lstm_seq_fwd_kernel(const float* __restrict__ pre, int64_t ldpre, int B, int T, 
                 const float a_o = pr[3 * (int64_t)H] + ((g & 1) ? acc[3][g / 2].y : acc[3][g / 2].x);
                 const float ig = sigmoidf_(a_i), fg = sigmoidf_(a_f), gg = tanhf_(a_g), og = sigmoidf_(a_o);
                 const float hold = hl[(size_t)j * G + g];
-                c[g] = fg * c[g] + ig * gg;
-                const float hn = og * tanhf_(c[g]);
-                hl[(size_t)j * G + g] = hn;
-                const float kp = keep ? keep[row * H + j] : 1.0f;
-                hseq[row * ldh + j] = f2bf(hn * kp);
-                if (t == T - 1) hlast[(int64_t)(b0 + g) * H + j] = hn;
-                if (gates) {
-                    float* gp = gates + row * H4 + j;
-                    gp[0] = ig;
-                    gp[H] = fg;
-                    gp[2 * (int64_t)H] = gg;
-                    gp[3 * (int64_t)H] = og;
-                    cseq[row * H + j] = c[g];
-                    hprev[row * ldhp + j] = f2bf(hold);
-                }
-            }
-        }
-        __syncthreads();  // h_t visible; partials consumed
-    }
-}
-
-// The inference recurrence over sequences of different lengths: sequence b owns rows row0[b] ..
-// row0[b] + len[b] - 1 of pre and hseq.  Same schedule, slice-order reduction and cell arithmetic as
-// lstm_seq_fwd_kernel, so every sequence comes out bit-identical to a dense launch on it alone (the
-// lanes of a packed FMA are independent).  The workgroup loops to the largest length of its group
-// (uniform: the barriers stay legal); a sequence past its end keeps its h in LDS untouched, reads no
-// row of pre and writes nothing.  hlast[b] = h of step len[b] - 1, zero for len[b] = 0.
-template <int G>
-__global__ void __launch_bounds__(kMaxThreads)
-lstm_seq_fwd_ragged_kernel(const float* __restrict__ pre, int64_t ldpre, int B, const int32_t* __restrict__ row0,
-                           const int32_t* __restrict__ len, int max_len, int H, const float* __restrict__ WT,
-                           uint16_t* __restrict__ hseq, int64_t ldh, float* __restrict__ hlast) {
-    extern __shared__ __align__(16) float smem[];
-    const int HP = (H + 63) & ~63;
-    const int S = kMaxThreads / HP;
-    const int j = threadIdx.x % HP, s = threadIdx.x / HP;
-    float* hl = smem;                      // [H][G]   h_{t-1} of the group
-    float* part = smem + (size_t)H * G;    // [S - 1][4 * G][HP] partial gate sums of slices 1 .. S-1
-    const int b0 = blockIdx.x * G;
-    const int nb = min(G, B - b0);
-    const int KC = (H + S - 1) / S;
-    const int k0 = s * KC, k1 = min(H, k0 + KC);
-    const bool unit = j < H;
-    const int64_t H4 = 4 * (int64_t)H;
-
-    int r0[G], ln[G];  // uniform over the workgroup
-    int T = 0;
-#pragma unroll
-    for (int g = 0; g < G; ++g) {
-        r0[g] = g < nb ? row0[b0 + g] : 0;
-        ln[g] = g < nb ? min(max(len[b0 + g], 0), max_len) : 0;
-        T = max(T, ln[g]);
-    }
-
-    float c[G];
-#pragma unroll
-    for (int g = 0; g < G; ++g) c[g] = 0.f;
-    for (int i = threadIdx.x; i < H * G; i += blockDim.x) hl[i] = 0.f;
-    if (s == 0 && unit) {
-#pragma unroll
-        for (int g = 0; g < G; ++g)
-            if (g < nb && ln[g] == 0) hlast[(int64_t)(b0 + g) * H + j] = 0.f;
-    }
-    __syncthreads();
-
-    for (int t = 0; t < T; ++t) {
-        v2f acc[4][G / 2];
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-#pragma unroll
-            for (int p = 0; p < G / 2; ++p) acc[q][p] = v2f{0.f, 0.f};
-        if (t > 0 && unit) {  // h_{-1} = 0
-            const float* w = WT + (int64_t)k0 * H4 + j;
-#pragma unroll 2
-            for (int k = k0; k < k1; ++k, w += H4) {
-                const float w0 = w[0], w1 = w[H], w2 = w[2 * (int64_t)H], w3 = w[3 * (int64_t)H];
-                const v2f* hv = reinterpret_cast<const v2f*>(hl + (size_t)k * G);
-#pragma unroll
-                for (int p = 0; p < G / 2; ++p) {
-                    const v2f h2 = hv[p];
-                    acc[0][p] += h2 * w0;
-                    acc[1][p] += h2 * w1;
-                    acc[2][p] += h2 * w2;
-                    acc[3][p] += h2 * w3;
-                }
-            }
-        }
-        if (s > 0) {
-            float* pp = part + (size_t)(s - 1) * 4 * G * HP + j;
-#pragma unroll
-            for (int q = 0; q < 4; ++q)
-#pragma unroll
-                for (int p = 0; p < G / 2; ++p) {
-                    pp[(size_t)(q * G + 2 * p) * HP] = acc[q][p].x;
-                    pp[(size_t)(q * G + 2 * p + 1) * HP] = acc[q][p].y;
-                }
-        }
-        __syncthreads();  // partials written; every read of h_{t-1} done
-        if (s == 0 && unit) {
-#pragma unroll 1
-            for (int r = 1; r < S; ++r) {
-                const float* pp = part + (size_t)(r - 1) * 4 * G * HP + j;
-#pragma unroll
-                for (int q = 0; q < 4; ++q)
-#pragma unroll
-                    for (int p = 0; p < G / 2; ++p) {
-                        acc[q][p].x += pp[(size_t)(q * G + 2 * p) * HP];
-                        acc[q][p].y += pp[(size_t)(q * G + 2 * p + 1) * HP];
-                    }
-            }
-#pragma unroll
-            for (int g = 0; g < G; ++g) {
-                if (t >= ln[g]) {  // past this sequence's end (ln = 0 for absent sequences)
-                    continue;
-                }
-                const int64_t row = (int64_t)r0[g] + t;
-                const float* pr = pre + row * ldpre + j;
-                const float a_i = pr[0] + ((g & 1) ? acc[0][g / 2].y : acc[0][g / 2].x);
-                const float a_f = pr[H] + ((g & 1) ? acc[1][g / 2].y : acc[1][g / 2].x);
-                const float a_g = pr[2 * (int64_t)H] + ((g & 1) ? acc[2][g / 2].y : acc[2][g / 2].x);
-                const float a_o = pr[3 * (int64_t)H] + ((g & 1) ? acc[3][g / 2].y : acc[3][g / 2].x);
-                const float ig = sigmoidf_(a_i), fg = sigmoidf_(a_f), gg = tanhf_(a_g), og = sigmoidf_(a_o);
-                // the dense kernel's contraction of fg * c + ig * gg, spelled out: left to the compiler, this
-                // kernel got one packed multiply of both products and an unfused add (a last-bit difference)
+                // explicit fmaf: the compiler's own contraction differed by a last bit between instantiations
                 c[g] = __builtin_fmaf(fg, c[g], ig * gg);
                 const float hn = og * tanhf_(c[g]);
                 hl[(size_t)j * G + g] = hn;
-                hseq[row * ldh + j] = f2bf(hn);
+                float hs = hn;  // what h_seq keeps: times keep in the dense train step
+                if constexpr (!RAGGED) hs *= keep ? keep[row * H + j] : 1.0f;
+                hseq[row * ldh + j] = f2bf(hs);
                 if (t == ln[g] - 1) hlast[(int64_t)(b0 + g) * H + j] = hn;
+                if constexpr (!RAGGED) {
+                    if (gates) {
+                        float* gp = gates + row * H4 + j;
+                        gp[0] = ig;
+                        gp[H] = fg;
+                        gp[2 * (int64_t)H] = gg;
+                        gp[3 * (int64_t)H] = og;
+                        cseq[row * H + j] = c[g];
+                        hprev[row * ldhp + j] = f2bf(hold);
+                    }
+                }
             }
         }
         __syncthreads();  // h_t visible; partials consumed
@@ -513,6 +439,23 @@ static const char* check_hidden(int64_t B, int64_t T, int64_t hidden) {
     return nullptr;
 }
 
+// The launch geometry of the recurrence kernels (the schedule in the header comment), in one place.
+struct SeqLaunch {
+    int H, G, HP, S;
+    unsigned grid, block;
+    SeqLaunch(int64_t B, int64_t hidden)
+        : H((int)hidden), G(group_of(hidden)), HP((H + 63) & ~63), S(kMaxThreads / HP), grid((unsigned)((B + G - 1) / G)),
+          block((unsigned)(S * HP)) {}
+    size_t lds_fwd() const { return ((size_t)H * G + (size_t)(S - 1) * 4 * G * HP) * sizeof(float); }  // hl + part
+    size_t lds_bwd() const { return ((size_t)4 * H * G + (size_t)(S - 1) * G * HP) * sizeof(float); }  // dl + part
+    // k4 / k2: the G = 4 and G = 2 instantiations of one kernel
+    template <typename K, typename... Args>
+    void run(K k4, K k2, size_t lds, hipStream_t stream, Args... args) const {
+        const K k = G == 4 ? k4 : k2;
+        k<<<grid, block, lds, stream>>>(args...);
+    }
+};
+
 }  // namespace lstm
 }  // namespace vc
 
@@ -563,16 +506,9 @@ int vc_lstm_seq_fwd(const float* pre, int64_t ldpre, int64_t B, int64_t T, int64
     if (ldpre < 4 * hidden || ldh < hidden) return fail(VC_ERR_INVALID_ARG, "vc_lstm_seq_fwd: row stride below the row length");
     if (gates && (!c_seq || !h_prev || ldhp < hidden))
         return fail(VC_ERR_INVALID_ARG, "vc_lstm_seq_fwd: the train variant needs gates, c_seq and h_prev (ldhp >= hidden)");
-    const int H = (int)hidden, G = group_of(hidden);
-    const int HP = (H + 63) & ~63, S = kMaxThreads / HP;
-    const size_t lds = ((size_t)H * G + (size_t)(S - 1) * 4 * G * HP) * sizeof(float);
-    const unsigned grid = (unsigned)((B + G - 1) / G), block = (unsigned)(S * HP);
-    if (G == 4)
-        lstm_seq_fwd_kernel<4><<<grid, block, lds, stream>>>(pre, ldpre, (int)B, (int)T, H, W_hh_t, keep, h_seq, ldh, h_last,
-                                                             gates, c_seq, h_prev, ldhp);
-    else
-        lstm_seq_fwd_kernel<2><<<grid, block, lds, stream>>>(pre, ldpre, (int)B, (int)T, H, W_hh_t, keep, h_seq, ldh, h_last,
-                                                             gates, c_seq, h_prev, ldhp);
+    const SeqLaunch L(B, hidden);
+    L.run(lstm_seq_fwd_kernel<4, false>, lstm_seq_fwd_kernel<2, false>, L.lds_fwd(), stream, pre, ldpre, (int)B, (int)T, L.H,
+          W_hh_t, nullptr, nullptr, keep, h_seq, ldh, h_last, gates, c_seq, h_prev, ldhp);
     return check_launch("vc_lstm_seq_fwd");
 }
 
@@ -585,16 +521,9 @@ int vc_lstm_seq_fwd_ragged(const float* pre, int64_t ldpre, int64_t B, const int
         return fail(VC_ERR_INVALID_ARG, std::string("vc_lstm_seq_fwd_ragged (T = max_len): ") + m);
     if (ldpre < 4 * hidden || ldh < hidden)
         return fail(VC_ERR_INVALID_ARG, "vc_lstm_seq_fwd_ragged: row stride below the row length");
-    const int H = (int)hidden, G = group_of(hidden);
-    const int HP = (H + 63) & ~63, S = kMaxThreads / HP;
-    const size_t lds = ((size_t)H * G + (size_t)(S - 1) * 4 * G * HP) * sizeof(float);
-    const unsigned grid = (unsigned)((B + G - 1) / G), block = (unsigned)(S * HP);
-    if (G == 4)
-        lstm_seq_fwd_ragged_kernel<4><<<grid, block, lds, stream>>>(pre, ldpre, (int)B, row0, len, (int)max_len, H, W_hh_t,
-                                                                    h_seq, ldh, h_last);
-    else
-        lstm_seq_fwd_ragged_kernel<2><<<grid, block, lds, stream>>>(pre, ldpre, (int)B, row0, len, (int)max_len, H, W_hh_t,
-                                                                    h_seq, ldh, h_last);
+    const SeqLaunch L(B, hidden);
+    L.run(lstm_seq_fwd_kernel<4, true>, lstm_seq_fwd_kernel<2, true>, L.lds_fwd(), stream, pre, ldpre, (int)B, (int)max_len,
+          L.H, W_hh_t, row0, len, nullptr, h_seq, ldh, h_last, nullptr, nullptr, nullptr, 0);
     return check_launch("vc_lstm_seq_fwd_ragged");
 }
 
@@ -604,16 +533,9 @@ int vc_lstm_seq_bwd(const float* gates, const float* c_seq, int64_t B, int64_t T
     if (!gates || !c_seq || !W_hh || !dh || !dpre || !dpre_bf16) return fail(VC_ERR_INVALID_ARG, "vc_lstm_seq_bwd: null pointer");
     if (const char* m = check_hidden(B, T, hidden)) return fail(VC_ERR_INVALID_ARG, std::string("vc_lstm_seq_bwd: ") + m);
     if (lddh < hidden || lddb < 4 * hidden) return fail(VC_ERR_INVALID_ARG, "vc_lstm_seq_bwd: row stride below the row length");
-    const int H = (int)hidden, G = group_of(hidden);
-    const int HP = (H + 63) & ~63, S = kMaxThreads / HP;
-    const size_t lds = ((size_t)4 * H * G + (size_t)(S - 1) * G * HP) * sizeof(float);
-    const unsigned grid = (unsigned)((B + G - 1) / G), block = (unsigned)(S * HP);
-    if (G == 4)
-        lstm_seq_bwd_kernel<4><<<grid, block, lds, stream>>>(gates, c_seq, (int)B, (int)T, H, W_hh, dh, lddh, last_only, keep,
-                                                             dpre, dpre_bf16, lddb);
-    else
-        lstm_seq_bwd_kernel<2><<<grid, block, lds, stream>>>(gates, c_seq, (int)B, (int)T, H, W_hh, dh, lddh, last_only, keep,
-                                                             dpre, dpre_bf16, lddb);
+    const SeqLaunch L(B, hidden);
+    L.run(lstm_seq_bwd_kernel<4>, lstm_seq_bwd_kernel<2>, L.lds_bwd(), stream, gates, c_seq, (int)B, (int)T, L.H, W_hh, dh,
+          lddh, last_only, keep, dpre, dpre_bf16, lddb);
     return check_launch("vc_lstm_seq_bwd");
 }
 

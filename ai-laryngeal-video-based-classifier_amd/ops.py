@@ -1031,6 +1031,20 @@ def video_to_cl_h16(video: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
     return out
 
 
+def _lstm_fwd_operands(name: str, rows: str, min_rows: int, B: int, hidden: int, pre, w_hh_t, h_seq, h_last) -> None:
+    """The operands lstm_seq_fwd and lstm_seq_fwd_ragged share; `rows` is how the entry point's messages
+    name the row count of pre / h_seq, min_rows what it asks of it here."""
+    _dev(pre, w_hh_t, h_seq, h_last)
+    _need(pre.dtype == torch.float32 and pre.dim() == 2 and pre.shape[0] >= min_rows and pre.shape[1] >= 4 * hidden and
+          pre.stride(1) == 1, f"{name}: pre f32 [{rows}, >= 4H]")
+    _need(w_hh_t.dtype == torch.float32 and w_hh_t.is_contiguous() and tuple(w_hh_t.shape) == (hidden, 4 * hidden),
+          f"{name}: w_hh_t f32 contiguous [H, 4H] (weight_hh transposed)")
+    _need(h_seq.dtype == torch.bfloat16 and h_seq.dim() == 2 and h_seq.shape[0] >= min_rows and h_seq.shape[1] >= hidden and
+          h_seq.stride(1) == 1, f"{name}: h_seq bf16 [{rows}, >= H]")
+    _need(h_last.dtype == torch.float32 and h_last.is_contiguous() and h_last.numel() >= B * hidden,
+          f"{name}: h_last f32 [B, H]")
+
+
 def lstm_seq_fwd(pre: torch.Tensor, B: int, T: int, hidden: int, w_hh_t: torch.Tensor, h_seq: torch.Tensor,
                  h_last: torch.Tensor, keep: torch.Tensor | None = None, gates: torch.Tensor | None = None,
                  c_seq: torch.Tensor | None = None, h_prev: torch.Tensor | None = None) -> torch.Tensor:
@@ -1039,15 +1053,7 @@ def lstm_seq_fwd(pre: torch.Tensor, B: int, T: int, hidden: int, w_hh_t: torch.T
     with gates / c_seq / h_prev (the train variant) the saved state of vc_lstm_seq_bwd."""
     _lstm_shape(B, T, hidden)
     M = B * T
-    _dev(pre, w_hh_t, h_seq, h_last)
-    _need(pre.dtype == torch.float32 and pre.dim() == 2 and pre.shape[0] >= M and pre.shape[1] >= 4 * hidden and
-          pre.stride(1) == 1, "lstm_seq_fwd: pre f32 [>= B*T, >= 4H]")
-    _need(w_hh_t.dtype == torch.float32 and w_hh_t.is_contiguous() and tuple(w_hh_t.shape) == (hidden, 4 * hidden),
-          "lstm_seq_fwd: w_hh_t f32 contiguous [H, 4H] (weight_hh transposed)")
-    _need(h_seq.dtype == torch.bfloat16 and h_seq.dim() == 2 and h_seq.shape[0] >= M and h_seq.shape[1] >= hidden and
-          h_seq.stride(1) == 1, "lstm_seq_fwd: h_seq bf16 [>= B*T, >= H]")
-    _need(h_last.dtype == torch.float32 and h_last.is_contiguous() and h_last.numel() >= B * hidden,
-          "lstm_seq_fwd: h_last f32 [B, H]")
+    _lstm_fwd_operands("lstm_seq_fwd", ">= B*T", M, B, hidden, pre, w_hh_t, h_seq, h_last)
     if keep is not None:
         _dev(keep)
         _need(keep.dtype == torch.float32 and keep.is_contiguous() and keep.numel() >= M * hidden and
@@ -1104,15 +1110,7 @@ def lstm_seq_fwd_ragged(pre: torch.Tensor, lengths, hidden: int, w_hh_t: torch.T
     else:
         row0 = tuple(int(r) for r in row0)
         _need(len(row0) == B and all(r >= 0 for r in row0), "lstm_seq_fwd_ragged: row0 must hold one row index >= 0 per sequence")
-    _dev(pre, w_hh_t, h_seq, h_last)
-    _need(pre.dtype == torch.float32 and pre.dim() == 2 and pre.shape[1] >= 4 * hidden and pre.stride(1) == 1,
-          "lstm_seq_fwd_ragged: pre f32 [rows, >= 4H]")
-    _need(w_hh_t.dtype == torch.float32 and w_hh_t.is_contiguous() and tuple(w_hh_t.shape) == (hidden, 4 * hidden),
-          "lstm_seq_fwd_ragged: w_hh_t f32 contiguous [H, 4H] (weight_hh transposed)")
-    _need(h_seq.dtype == torch.bfloat16 and h_seq.dim() == 2 and h_seq.shape[1] >= hidden and h_seq.stride(1) == 1,
-          "lstm_seq_fwd_ragged: h_seq bf16 [rows, >= H]")
-    _need(h_last.dtype == torch.float32 and h_last.is_contiguous() and h_last.numel() >= B * hidden,
-          "lstm_seq_fwd_ragged: h_last f32 [B, H]")
+    _lstm_fwd_operands("lstm_seq_fwd_ragged", "rows", 0, B, hidden, pre, w_hh_t, h_seq, h_last)
     rows = min(pre.shape[0], h_seq.shape[0])
     _need(all(r + n <= rows for r, n in zip(row0, lengths)) and rows < 2 ** 31,
           f"lstm_seq_fwd_ragged: a sequence runs past the {rows} rows of pre / h_seq")

@@ -130,21 +130,11 @@ class VideoResNet50LSTM(torch.nn.Module):
         self._packed = pk
         return pk
 
-    def _workspace(self, B, T, device):
-        key = (B, T, str(device))
+    def _workspace(self, rows, B, device):
+        """The inference buffers for `rows` frame rows in all and B sequences; one (rows, B) at a time."""
+        key = (rows, B, str(device))
         if key not in self._ws:
-            M = _ru(B * T, 256)
-            z = lambda r, c, dt: torch.zeros(r, c, dtype=dt, device=device)  # noqa: E731
-            self._ws = {key: dict(pre=z(M, _ru(4 * self.hidden, 128), torch.float32),
-                                  hseq=[z(M, _ru(self.hidden, 128), torch.bfloat16) for _ in range(2)],
-                                  hlast=z(B, self.hidden, torch.float32), logits=z(B, 1, torch.float32))}
-        return self._ws[key]
-
-    def _workspace_ragged(self, N, B, device):
-        """forward_ragged's buffers: N frame rows in all, B sequences; one (N, B) at a time, like _workspace."""
-        key = ("ragged", N, B, str(device))
-        if key not in self._ws:
-            M = _ru(N, 256)
+            M = _ru(rows, 256)
             z = lambda r, c, dt: torch.zeros(r, c, dtype=dt, device=device)  # noqa: E731
             self._ws = {key: dict(pre=z(M, _ru(4 * self.hidden, 128), torch.float32),
                                   hseq=[z(M, _ru(self.hidden, 128), torch.bfloat16) for _ in range(2)],
@@ -276,14 +266,26 @@ class VideoResNet50LSTM(torch.nn.Module):
 
     def forward_logits(self, video: torch.Tensor) -> torch.Tensor:
         """Inference: logits f32 [B, 1] (a workspace buffer, overwritten by the next call)."""
-        B, _, T = video.shape[:3]
-        pk = self._pack(video.device)
-        ws = self._workspace(B, T, video.device)
-        inp = self.features(video)
+        return self._infer(video)
+
+    def _infer(self, x: torch.Tensor, lengths=None) -> torch.Tensor:
+        """The inference path on the frames of x: the backbone, per LSTM layer the projection GEMM over all
+        rows and the recurrence (dense over x's B sequences of T frames when lengths is None; else x is
+        [1, 3, N, H, W] and the recurrence ragged over `lengths`), then the head.  Returns the workspace's
+        logits buffer."""
+        B, _, T = x.shape[:3]
+        nseq = B if lengths is None else len(lengths)
+        pk = self._pack(x.device)
+        ws = self._workspace(B * T, nseq, x.device)
+        inp = self.features(x)
         for l, L in enumerate(pk["layers"]):
+            hseq = ws["hseq"][l & 1]
             ops.gemm(inp, L["wb"], L["b"], "bias_f32", ws["pre"], op="lstm_ih")
-            ops.lstm_seq_fwd(ws["pre"], B, T, self.hidden, L["w_hh_t"], ws["hseq"][l & 1], ws["hlast"])
-            inp = ws["hseq"][l & 1]
+            if lengths is None:
+                ops.lstm_seq_fwd(ws["pre"], B, T, self.hidden, L["w_hh_t"], hseq, ws["hlast"])
+            else:
+                ops.lstm_seq_fwd_ragged(ws["pre"], lengths, self.hidden, L["w_hh_t"], hseq, ws["hlast"])
+            inp = hseq
         w1, b1, w2, b2 = pk["head"]
         return ops.mlp_head_fwd(ws["hlast"], w1, b1, w2, b2, ws["logits"])
 
@@ -304,17 +306,8 @@ class VideoResNet50LSTM(torch.nn.Module):
         if not lengths or min(lengths) < 1 or sum(lengths) != video.shape[2]:
             raise ValueError(f"lengths {lengths} must be >= 1 and sum to the {video.shape[2]} frames of video")
         x = video.contiguous().float() if video.dtype != torch.float32 else video.contiguous()
-        N, B = x.shape[2], len(lengths)
         with torch.no_grad():
-            pk = self._pack(x.device)
-            ws = self._workspace_ragged(N, B, x.device)
-            inp = self.features(x)
-            for l, L in enumerate(pk["layers"]):
-                ops.gemm(inp, L["wb"], L["b"], "bias_f32", ws["pre"], op="lstm_ih")
-                ops.lstm_seq_fwd_ragged(ws["pre"], lengths, self.hidden, L["w_hh_t"], ws["hseq"][l & 1], ws["hlast"])
-                inp = ws["hseq"][l & 1]
-            w1, b1, w2, b2 = pk["head"]
-            return ops.mlp_head_fwd(ws["hlast"], w1, b1, w2, b2, ws["logits"]).clone()
+            return self._infer(x, lengths).clone()
 
     def _forward_train(self, video: torch.Tensor) -> torch.Tensor:
         B, _, T = video.shape[:3]

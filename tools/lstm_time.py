@@ -1,16 +1,12 @@
 """Timing of the ResNet50-LSTM recurrence kernels at the workload shape (B = 4, T = 32, hidden 256;
 layer 0 with Din 2048, layer 1 with Din 256).
 
-  python tools/lstm_gpu/build.py          # the round-3 prototype, the baseline (tools/lstm_gpu/liblstm.so)
   python tools/lstm_time.py [--out profiles/lstm_time.json] [--reps 100] [--no-step]
 
-The new forward (vc_lstm_seq_fwd of libvclip.so) is timed against the prototype's vc_lstm_recurrence on
-the same `pre` and W_hh: device events after warm-up, the two kernels alternating within this process,
-the median of `--reps` (>= 50) repetitions.  The prototype alone is also timed before and after that
-loop; the spread of those two medians is the margin.  The bar: new median <= prototype median + margin
-(exit status 1 otherwise).  Also reported, without a bar: the train variant, the backward kernel
-(vc_lstm_seq_bwd, full and last-step-only) and the whole train step (forward, BCE-with-logits loss,
-backward, AdamW) at B = 4, T = 32, 224 x 224.
+Device events after warm-up, the median of `--reps` (>= 50) repetitions of each: the forward
+(vc_lstm_seq_fwd of libvclip.so), its train variant, the backward kernel (vc_lstm_seq_bwd, full and
+last-step-only) and, unless --no-step, the whole train step (forward, BCE-with-logits loss, backward,
+AdamW) at B = 4, T = 32, 224 x 224.  A report without a bar: compare two builds by running it on each.
 """
 from __future__ import annotations
 
@@ -24,7 +20,6 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tools", "lstm_gpu"))
 
 B, T, H = 4, 32, 256
 DEV = "cuda"
@@ -55,7 +50,6 @@ def main() -> int:
     a = ap.parse_args()
     reps = max(50, a.reps)
 
-    import lstm_model as proto  # tools/lstm_gpu: raises if liblstm.so is not built
     from vclip_amd import autograd_ops as A
     from vclip_amd import ops
     from vclip_amd.build import source_hash
@@ -65,7 +59,6 @@ def main() -> int:
     k = 1.0 / H ** 0.5
     res = {"shape": dict(B=B, T=T, hidden=H), "reps": reps, "build": source_hash(),
            "device": torch.cuda.get_device_name(0), "layers": {}}
-    ok = True
     for name, din in (("l0", 2048), ("l1", 256)):
         w_ih = ((torch.rand(4 * H, din, generator=g) * 2 - 1) * k).to(DEV)
         w_hh = ((torch.rand(4 * H, H, generator=g) * 2 - 1) * k).to(DEV)
@@ -74,42 +67,22 @@ def main() -> int:
         pre = torch.empty(256, 4 * H, device=DEV)
         ops.gemm(x, pk["wb"], torch.zeros(4 * H, device=DEV), "bias_f32", pre)
         z = lambda r, c, dt=torch.float32: torch.zeros(r, c, dtype=dt, device=DEV)  # noqa: E731
-        hs_n, hl_n, hs_p, hl_p = z(M, H, torch.bfloat16), z(B, H), z(M, H, torch.bfloat16), z(B, H)
+        hseq, hlast = z(M, H, torch.bfloat16), z(B, H)
         gates, cseq, hprev = z(M, 4 * H), z(M, H), z(M, H, torch.bfloat16)
-        new = lambda: ops.lstm_seq_fwd(pre, B, T, H, pk["w_hh_t"], hs_n, hl_n)  # noqa: E731
-        new_train = lambda: ops.lstm_seq_fwd(pre, B, T, H, pk["w_hh_t"], hs_n, hl_n, gates=gates, c_seq=cseq,  # noqa: E731
+        fwd = lambda: ops.lstm_seq_fwd(pre, B, T, H, pk["w_hh_t"], hseq, hlast)  # noqa: E731
+        fwd_train = lambda: ops.lstm_seq_fwd(pre, B, T, H, pk["w_hh_t"], hseq, hlast, gates=gates, c_seq=cseq,  # noqa: E731
                                              h_prev=hprev)
-        old = lambda: proto.lstm_recurrence(pre, B, T, H, pk["w_hh"], hs_p, hl_p)  # noqa: E731
-        p_start = _median(old, reps)
-        for _ in range(10):
-            new()
-            old()
-        torch.cuda.synchronize()
-        tn, tp = [], []
-        for _ in range(reps):
-            tn.append(_time(new))
-            tp.append(_time(old))
-        p_end = _median(old, reps)
-        same = float((hl_n - hl_p).abs().max())
-        new_us, proto_us = statistics.median(tn), statistics.median(tp)
-        margin = abs(p_start - p_end)
+        fwd_train()  # the saved state the backward reads
         # the backward: full dh_seq (lower layers) and last step only (top layer)
-        new_train()
         dh, dhl = torch.randn(M, H, generator=g).to(DEV), torch.randn(B, H, generator=g).to(DEV)
         dpre, dpb = z(M, 4 * H), z(M, 4 * H, torch.bfloat16)
-        r = dict(din=din, new_fwd_us=new_us, proto_fwd_us=proto_us, proto_start_us=p_start, proto_end_us=p_end,
-                 margin_us=margin, new_fwd_min_us=min(tn), proto_fwd_min_us=min(tp), max_abs_h_last_diff=same,
-                 new_fwd_train_us=_median(new_train, reps),
+        r = dict(din=din, fwd_us=_median(fwd, reps), fwd_train_us=_median(fwd_train, reps),
                  bwd_full_us=_median(lambda: ops.lstm_seq_bwd(gates, cseq, B, T, H, pk["w_hh"], dh, dpre, dpb), reps),
                  bwd_last_only_us=_median(lambda: ops.lstm_seq_bwd(gates, cseq, B, T, H, pk["w_hh"], dhl, dpre, dpb,
                                                                     last_only=True), reps))
-        r["pass"] = bool(new_us <= proto_us + margin and same < 1e-4)
-        ok = ok and r["pass"]
         res["layers"][name] = r
-        print(f"{name} (Din {din}): new fwd {new_us:.1f} us, prototype {proto_us:.1f} us "
-              f"(alone: {p_start:.1f} before, {p_end:.1f} after; margin {margin:.1f}) -> "
-              f"{'PASS' if r['pass'] else 'FAIL'}; train fwd {r['new_fwd_train_us']:.1f} us, bwd {r['bwd_full_us']:.1f} us, "
-              f"bwd last-only {r['bwd_last_only_us']:.1f} us", flush=True)
+        print(f"{name} (Din {din}): fwd {r['fwd_us']:.1f} us, train fwd {r['fwd_train_us']:.1f} us, "
+              f"bwd {r['bwd_full_us']:.1f} us, bwd last-only {r['bwd_last_only_us']:.1f} us", flush=True)
 
     if not a.no_step:
         import torch.nn.functional as F
@@ -140,13 +113,12 @@ def main() -> int:
         res["eval_forward_ms"] = _median(lambda: model(video), 7, warmup=2) / 1e3
         print(f"train step B={B} T={T} 224^2: {res['train_step_ms']:.2f} ms (LSTM + head + AdamW part "
               f"{res['train_step_lstm_head_ms']:.2f} ms); eval forward {res['eval_forward_ms']:.2f} ms", flush=True)
-    res["pass"] = ok
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as f:
         json.dump(res, f, indent=1)
         f.write("\n")
-    print(json.dumps({"pass": ok, "out": a.out}))
-    return 0 if ok else 1
+    print(json.dumps({"out": a.out}))
+    return 0
 
 
 if __name__ == "__main__":
