@@ -534,6 +534,13 @@ LSTM_HISTORY_KEYS = ("train_loss", "val_loss", "train_acc", "val_acc", "train_au
 # batched ragged inference: the smallest batch within 5 % of the best measured rate, which was the largest
 # measured (16 videos per call 2211 videos/s, 8 per call 1907, one at a time 656)
 LSTM_VIDEOS_PER_BATCH = 16
+LSTM_STREAM_CHUNK_HELP = (
+    "0 (default): off, the sampled-frames inference of the reference.  N >= 1: every frame of every video goes "
+    "through the model, up to --videos_per_batch videos in lockstep, at most N frames of each per forward_stream "
+    "call with the LSTM state carried between calls (--sampling_method and --sequence_length are ignored); also "
+    "writes frame_probabilities/<video>.csv.  128 is the smallest chunk within 5 %% of the best measured rate "
+    "(4 videos of 256 frames: 41.0k frames/s at 9.2 GB peak; 32: 36.9k at 2.9 GB; 256: 41.9k at 17.1 GB, "
+    "DESIGN.md section 5.11).")
 
 
 def build_parser_lstm(inference: bool):
@@ -550,6 +557,8 @@ def build_parser_lstm(inference: bool):
         p.add_argument("--single_video", type=str, default=None)
         # not in the reference, which runs one video per forward: videos per forward_ragged call
         p.add_argument("--videos_per_batch", type=int, default=LSTM_VIDEOS_PER_BATCH)
+        # not in the reference either: whole-video streaming inference (forward_stream with the LSTM state carried)
+        p.add_argument("--stream_chunk", type=int, default=0, help=LSTM_STREAM_CHUNK_HELP)
         return p
     p = argparse.ArgumentParser(description="ResNet50-LSTM video classification training (libvclip, MI355X)")
     p.add_argument("--data_dir", type=str, default="dataset")  # resnet50-2d-lstm/main.py:22-62
@@ -894,6 +903,34 @@ def _lstm_load_video(path, method, sequence_length, device):
     return pp.lstm_inference_preprocess(frames), idx, total
 
 
+def lstm_stream_videos(model, sources, chunk, device):
+    """Whole-video inference over opened videos (video_io sources) in lockstep: every round reads the next
+    <= chunk frames of each, resizes and normalises them on the GPU as _lstm_load_video does, and makes one
+    forward_stream call with the carried state; a finished video takes length 0 and keeps its logit.
+    Returns (probabilities, one per video; per-frame probability lists, total_frames entries each)."""
+    from . import preprocess as pp
+    totals = [int(s.total_frames) for s in sources]
+    pos = [0] * len(sources)
+    frame_probs = [[] for _ in sources]
+    state, logits = None, None
+    while any(p < t for p, t in zip(pos, totals)):
+        lens = [min(chunk, t - p) for p, t in zip(pos, totals)]
+        parts = [np.ascontiguousarray(s.read(list(range(p, p + n)))) for s, p, n in zip(sources, pos, lens) if n]
+        sizes = {a.shape[1:3] for a in parts}
+        if len(sizes) == 1:  # one resize over the round's frames
+            frames = pp.cv2_resize_u8(torch.from_numpy(np.concatenate(parts)).to(device), (224, 224))
+        else:
+            frames = torch.cat([pp.cv2_resize_u8(torch.from_numpy(a).to(device), (224, 224)) for a in parts])
+        logits, state, fl = model.forward_stream(pp.lstm_inference_preprocess(frames), lens, state, frame_logits=True)
+        fp = torch.sigmoid(fl.float()).reshape(-1).tolist()
+        at = 0
+        for b, n in enumerate(lens):
+            frame_probs[b].extend(fp[at:at + n])
+            at += n
+            pos[b] += n
+    return torch.sigmoid(logits.float()).reshape(-1).tolist(), frame_probs
+
+
 def _write_csv(rows, path):
     """pd.DataFrame(rows).to_csv(path, index=False) (inference.py:310-321); the csv module where pandas is absent."""
     try:
@@ -910,8 +947,11 @@ def _write_csv(rows, path):
 
 def run_inference_lstm(argv=None):
     """resnet50-2d-lstm/inference.py on batched ragged inference: up to --videos_per_batch videos, each with
-    its own (clamped) frame count, go through one `forward_ragged`.  Returns the summary dict (None when no
-    video was found or none succeeded), with the experiment directory under "output_dir"."""
+    its own (clamped) frame count, go through one `forward_ragged`.  With --stream_chunk N >= 1 instead every
+    video is read whole and the videos of a batch advance in lockstep through `forward_stream`, <= N frames each
+    per call (lstm_stream_videos); frame_probabilities/<video>.csv and summary["stream_chunk"] are added.
+    Returns the summary dict (None when no video was found or none succeeded), with the experiment directory
+    under "output_dir"."""
     import os
     args = build_parser_lstm(inference=True).parse_args(argv)
     exp = LstmExperimentLogger(os.path.join(args.output_dir, f"inference_{datetime.now().strftime('%Y%m%d_%H%M%S')}"),
@@ -922,6 +962,11 @@ def run_inference_lstm(argv=None):
         logger.warning("--visualize: plots are not part of this build; the CSV / JSON results are written as usual")
     if args.videos_per_batch < 1:
         raise ValueError("--videos_per_batch must be >= 1")
+    if args.stream_chunk < 0:
+        raise ValueError("--stream_chunk must be >= 0 (0: off)")
+    if args.stream_chunk:
+        logger.info(f"--stream_chunk {args.stream_chunk}: every frame of every video goes through the model, "
+                    "--sampling_method and --sequence_length are ignored")
     device = _device()
     model = lstm_model_from_checkpoint(args.model_path, device)
     video_files = lstm_inference_videos(args)
@@ -954,18 +999,44 @@ def run_inference_lstm(argv=None):
                           "probability": float(p), "sampled_frames": len(idx), "total_frames": total,
                           "frame_indices": idx, "status": "success"}
 
+    def flush_stream(batch):
+        if not batch:
+            return
+        try:
+            probs, frame_probs = lstm_stream_videos(model, [src for _, src in batch], args.stream_chunk, device)
+        except Exception as e:  # noqa: BLE001 - the whole group failed: its videos get the error row
+            for k, _ in batch:
+                results[k] = error_row(video_files[k], e)
+            return
+        fp_dir = out_dir / "frame_probabilities"
+        fp_dir.mkdir(exist_ok=True)
+        for (k, src), p, fp in zip(batch, probs, frame_probs):
+            name = os.path.basename(video_files[k])
+            if (fp_dir / f"{name}.csv").exists():  # the same file name in two folders
+                name = f"{k}_{name}"
+            _write_csv([{"frame": i, "probability": v} for i, v in enumerate(fp)], fp_dir / f"{name}.csv")
+            results[k] = {"video_path": video_files[k], "prediction": "referral" if p >= 0.5 else "non_referral",
+                          "probability": float(p), "sampled_frames": src.total_frames, "total_frames": src.total_frames,
+                          "frame_indices": "all", "status": "success"}
+
     batch = []
     for k, path in enumerate(video_files):
         try:  # a video that fails to open or decode does not take its batch down (inference.py:196-203)
-            clip, idx, total = _lstm_load_video(path, args.sampling_method, args.sequence_length, device)
+            if args.stream_chunk:
+                src = video_io.open_video(path)
+                if src.total_frames < 1:
+                    raise ValueError("the video has no frames")
+                batch.append((k, src))
+            else:
+                clip, idx, total = _lstm_load_video(path, args.sampling_method, args.sequence_length, device)
+                batch.append((k, clip, idx, total))
         except Exception as e:  # noqa: BLE001
             results[k] = error_row(path, e)
             continue
-        batch.append((k, clip, idx, total))
         if len(batch) == args.videos_per_batch:
-            flush(batch)
+            (flush_stream if args.stream_chunk else flush)(batch)
             batch = []
-    flush(batch)
+    (flush_stream if args.stream_chunk else flush)(batch)
     for r in results:
         name = os.path.basename(r["video_path"])
         if r["status"] == "success":
@@ -983,6 +1054,8 @@ def run_inference_lstm(argv=None):
                "non_referral_cases": sum(1 for r in ok if r["prediction"] == "non_referral"),
                "sampling_method": args.sampling_method, "sequence_length": args.sequence_length,
                "model_path": args.model_path}
+    if args.stream_chunk:
+        summary["stream_chunk"] = args.stream_chunk
     _write_csv(ok, out_dir / "inference_results.csv")
     if failed:
         _write_csv(failed, out_dir / "inference_failures.csv")

@@ -4,9 +4,9 @@
 // split-K wgrad GEMMs) and the Linear -> ReLU -> Dropout -> Linear head, forward and backward.
 //
 // There are two recurrence kernels, one forward and one backward.  The forward one is a template over
-// <G, RAGGED>: dense inference, dense train (gates != nullptr) and the ragged inference over
-// sequences of different lengths are instantiations of one step loop, so a sequence comes out
-// bit-identical whichever entry ran it.  Both kernels share one schedule, whose launch geometry the
+// <G, RAGGED, STATE>: dense inference, dense train (gates != nullptr), the ragged inference over
+// sequences of different lengths and the stateful inference ((h0, c0) in, (h_n, c_n) out) are
+// instantiations of one step loop, so a sequence comes out bit-identical whichever entry ran it.  Both kernels share one schedule, whose launch geometry the
 // host keeps in SeqLaunch.  A workgroup owns G whole sequences (G = 4 for
 // hidden <= 512, else 2) from the first step to the last, so there is no cross-workgroup barrier.
 // HP = hidden rounded up to 64; the block has S * HP threads, S = 1024 / HP.  Thread (s, j) owns
@@ -100,12 +100,20 @@ __global__ void __launch_bounds__(256) video_to_cl_h16_kernel(const float* __res
 // row of pre and writes nothing; hlast[b] = 0 for len[b] = 0.  The step loop is the dense one and
 // the lanes of a packed FMA are independent, so every sequence comes out bit-identical to a dense
 // launch on it alone.
-template <int G, bool RAGGED>
+// Stateful (STATE = true, with RAGGED = true; inference only): row0 == nullptr selects the dense rows.
+// h_{-1} = h0[b], c_{-1} = c0[b] (both nullptr: zero, and step 0 skips the W_hh product as above);
+// hfin[b] / cfin[b] = h / c after the last step, the incoming state for len[b] = 0; hall (optional) = the
+// unrounded h of every step.  hfin may alias h0 and cfin c0: the workgroup owns its sequences and has h0
+// in LDS and c0 in registers before its first store, so these four carry no __restrict__.  hlast is
+// not touched.  STATE = false compiles all of it out.
+template <int G, bool RAGGED, bool STATE = false>
 __global__ void __launch_bounds__(kMaxThreads)
 lstm_seq_fwd_kernel(const float* __restrict__ pre, int64_t ldpre, int B, int T, int H, const float* __restrict__ WT,
                     const int32_t* __restrict__ row0, const int32_t* __restrict__ len, const float* __restrict__ keep,
                     uint16_t* __restrict__ hseq, int64_t ldh, float* __restrict__ hlast, float* __restrict__ gates,
-                    float* __restrict__ cseq, uint16_t* __restrict__ hprev, int64_t ldhp) {
+                    float* __restrict__ cseq, uint16_t* __restrict__ hprev, int64_t ldhp, const float* h0, const float* c0,
+                    float* hfin, float* cfin, float* __restrict__ hall, int64_t ldha) {
+    static_assert(RAGGED || !STATE, "the stateful instantiations are the ragged ones");
     extern __shared__ __align__(16) float smem[];
     const int HP = (H + 63) & ~63;
     const int S = kMaxThreads / HP;
@@ -124,7 +132,7 @@ lstm_seq_fwd_kernel(const float* __restrict__ pre, int64_t ldpre, int B, int T, 
     int steps = 0;
 #pragma unroll
     for (int g = 0; g < G; ++g) {
-        if constexpr (RAGGED) {
+        if (RAGGED && !(STATE && !row0)) {
             r0[g] = g < nb ? row0[b0 + g] : 0;
             ln[g] = g < nb ? min(max(len[b0 + g], 0), T) : 0;
         } else {
@@ -137,8 +145,21 @@ lstm_seq_fwd_kernel(const float* __restrict__ pre, int64_t ldpre, int B, int T, 
     float c[G];
 #pragma unroll
     for (int g = 0; g < G; ++g) c[g] = 0.f;
-    for (int i = threadIdx.x; i < H * G; i += blockDim.x) hl[i] = 0.f;
-    if constexpr (RAGGED) {
+    const bool carried = STATE && h0;  // uniform: a state came in, so step 0 has a W_hh product
+    if (carried) {
+        for (int i = threadIdx.x; i < H * G; i += blockDim.x) {
+            const int k = i / G, g = i % G;
+            hl[i] = g < nb ? h0[(int64_t)(b0 + g) * H + k] : 0.f;
+        }
+        if (s == 0 && unit) {
+#pragma unroll
+            for (int g = 0; g < G; ++g)
+                if (g < nb) c[g] = c0[(int64_t)(b0 + g) * H + j];
+        }
+    } else {
+        for (int i = threadIdx.x; i < H * G; i += blockDim.x) hl[i] = 0.f;
+    }
+    if constexpr (RAGGED && !STATE) {
         if (s == 0 && unit) {
 #pragma unroll
             for (int g = 0; g < G; ++g)
@@ -146,6 +167,16 @@ lstm_seq_fwd_kernel(const float* __restrict__ pre, int64_t ldpre, int B, int T, 
         }
     }
     __syncthreads();
+    if constexpr (STATE) {  // after the barrier: every read of h0 / c0 is done, hfin / cfin may alias them
+        if (s == 0 && unit) {
+#pragma unroll
+            for (int g = 0; g < G; ++g)
+                if (g < nb && ln[g] == 0) {  // the state passes through, also when the step loop never runs
+                    hfin[(int64_t)(b0 + g) * H + j] = hl[(size_t)j * G + g];
+                    cfin[(int64_t)(b0 + g) * H + j] = c[g];
+                }
+        }
+    }
 
     for (int t = 0; t < steps; ++t) {
         // acc[gate][pair] = sum over this slice's k of W_hh[gate*H + j][k] * h_{t-1}[k]
@@ -154,7 +185,7 @@ lstm_seq_fwd_kernel(const float* __restrict__ pre, int64_t ldpre, int B, int T, 
         for (int q = 0; q < 4; ++q)
 #pragma unroll
             for (int p = 0; p < G / 2; ++p) acc[q][p] = v2f{0.f, 0.f};
-        if (t > 0 && unit) {  // h_{-1} = 0
+        if ((t > 0 || carried) && unit) {  // h_{-1} = 0 without a carried state
             const float* w = WT + (int64_t)k0 * H4 + j;
 #pragma unroll 2
             for (int k = k0; k < k1; ++k, w += H4) {
@@ -213,7 +244,15 @@ lstm_seq_fwd_kernel(const float* __restrict__ pre, int64_t ldpre, int B, int T, 
                 float hs = hn;  // what h_seq keeps: times keep in the dense train step
                 if constexpr (!RAGGED) hs *= keep ? keep[row * H + j] : 1.0f;
                 hseq[row * ldh + j] = f2bf(hs);
-                if (t == ln[g] - 1) hlast[(int64_t)(b0 + g) * H + j] = hn;
+                if constexpr (STATE) {
+                    if (hall) hall[row * ldha + j] = hn;
+                    if (t == ln[g] - 1) {
+                        hfin[(int64_t)(b0 + g) * H + j] = hn;
+                        cfin[(int64_t)(b0 + g) * H + j] = c[g];
+                    }
+                } else {
+                    if (t == ln[g] - 1) hlast[(int64_t)(b0 + g) * H + j] = hn;
+                }
                 if constexpr (!RAGGED) {
                     if (gates) {
                         float* gp = gates + row * H4 + j;
@@ -508,7 +547,8 @@ int vc_lstm_seq_fwd(const float* pre, int64_t ldpre, int64_t B, int64_t T, int64
         return fail(VC_ERR_INVALID_ARG, "vc_lstm_seq_fwd: the train variant needs gates, c_seq and h_prev (ldhp >= hidden)");
     const SeqLaunch L(B, hidden);
     L.run(lstm_seq_fwd_kernel<4, false>, lstm_seq_fwd_kernel<2, false>, L.lds_fwd(), stream, pre, ldpre, (int)B, (int)T, L.H,
-          W_hh_t, nullptr, nullptr, keep, h_seq, ldh, h_last, gates, c_seq, h_prev, ldhp);
+          W_hh_t, nullptr, nullptr, keep, h_seq, ldh, h_last, gates, c_seq, h_prev, ldhp, nullptr, nullptr, nullptr, nullptr,
+          nullptr, 0);
     return check_launch("vc_lstm_seq_fwd");
 }
 
@@ -523,8 +563,29 @@ int vc_lstm_seq_fwd_ragged(const float* pre, int64_t ldpre, int64_t B, const int
         return fail(VC_ERR_INVALID_ARG, "vc_lstm_seq_fwd_ragged: row stride below the row length");
     const SeqLaunch L(B, hidden);
     L.run(lstm_seq_fwd_kernel<4, true>, lstm_seq_fwd_kernel<2, true>, L.lds_fwd(), stream, pre, ldpre, (int)B, (int)max_len,
-          L.H, W_hh_t, row0, len, nullptr, h_seq, ldh, h_last, nullptr, nullptr, nullptr, 0);
+          L.H, W_hh_t, row0, len, nullptr, h_seq, ldh, h_last, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr,
+          nullptr, nullptr, 0);
     return check_launch("vc_lstm_seq_fwd_ragged");
+}
+
+int vc_lstm_seq_fwd_state(const float* pre, int64_t ldpre, int64_t B, const int32_t* row0, const int32_t* len,
+                          int64_t max_len, int64_t hidden, const float* W_hh_t, const float* h0, const float* c0,
+                          uint16_t* h_seq, int64_t ldh, float* h_all, int64_t ldha, float* h_n, float* c_n,
+                          hipStream_t stream) {
+    if (!pre || !W_hh_t || !h_seq || !h_n || !c_n) return fail(VC_ERR_INVALID_ARG, "vc_lstm_seq_fwd_state: null pointer");
+    if (!row0 != !len)
+        return fail(VC_ERR_INVALID_ARG, "vc_lstm_seq_fwd_state: row0 and len come together (both null: the dense layout)");
+    if (!h0 != !c0)
+        return fail(VC_ERR_INVALID_ARG, "vc_lstm_seq_fwd_state: h0 and c0 come together (both null: the zero state)");
+    if (const char* m = check_hidden(B, max_len, hidden))
+        return fail(VC_ERR_INVALID_ARG, std::string("vc_lstm_seq_fwd_state (T = max_len): ") + m);
+    if (ldpre < 4 * hidden || ldh < hidden || (h_all && ldha < hidden))
+        return fail(VC_ERR_INVALID_ARG, "vc_lstm_seq_fwd_state: row stride below the row length");
+    const SeqLaunch L(B, hidden);
+    L.run(lstm_seq_fwd_kernel<4, true, true>, lstm_seq_fwd_kernel<2, true, true>, L.lds_fwd(), stream, pre, ldpre, (int)B,
+          (int)max_len, L.H, W_hh_t, row0, len, nullptr, h_seq, ldh, nullptr, nullptr, nullptr, nullptr, 0, h0, c0, h_n, c_n,
+          h_all, ldha);
+    return check_launch("vc_lstm_seq_fwd_state");
 }
 
 int vc_lstm_seq_bwd(const float* gates, const float* c_seq, int64_t B, int64_t T, int64_t hidden, const float* W_hh,

@@ -1090,6 +1090,31 @@ def _ragged_tables(lengths: tuple, row0: tuple, device) -> tuple:
     return tab
 
 
+def _ragged_row0(name: str, lengths: tuple, row0) -> tuple:
+    """row0 as host ints, one per sequence; None = the exclusive prefix sum of lengths (back to back)."""
+    if row0 is None:
+        acc, r = 0, []
+        for n in lengths:
+            r.append(acc)
+            acc += n
+        return tuple(r)
+    row0 = tuple(int(r) for r in row0)
+    _need(len(row0) == len(lengths) and all(r >= 0 for r in row0), f"{name}: row0 must hold one row index >= 0 per sequence")
+    return row0
+
+
+def _ragged_inside(name: str, lengths: tuple, row0: tuple, rows: int, what: str) -> None:
+    """Every sequence lies inside the `rows` rows of the buffers and no two overlap (an empty sequence owns no row)."""
+    _need(all(r + n <= rows for r, n in zip(row0, lengths)) and rows < 2 ** 31,
+          f"{name}: a sequence runs past the {rows} rows of {what}")
+    end = 0
+    for r, n in sorted(zip(row0, lengths)):
+        if n == 0:
+            continue
+        _need(r >= end, f"{name}: two sequences overlap")
+        end = r + n
+
+
 def lstm_seq_fwd_ragged(pre: torch.Tensor, lengths, hidden: int, w_hh_t: torch.Tensor, h_seq: torch.Tensor,
                         h_last: torch.Tensor, row0=None) -> torch.Tensor:
     """The inference recurrence over len(lengths) sequences of different lengths: sequence b owns rows
@@ -1101,23 +1126,9 @@ def lstm_seq_fwd_ragged(pre: torch.Tensor, lengths, hidden: int, w_hh_t: torch.T
     B = len(lengths)
     _need(B >= 1 and all(n >= 1 for n in lengths), "lstm_seq_fwd_ragged: lengths must be a non-empty sequence of ints >= 1")
     _lstm_shape(B, max(lengths), hidden)
-    if row0 is None:
-        acc, r = 0, []
-        for n in lengths:
-            r.append(acc)
-            acc += n
-        row0 = tuple(r)
-    else:
-        row0 = tuple(int(r) for r in row0)
-        _need(len(row0) == B and all(r >= 0 for r in row0), "lstm_seq_fwd_ragged: row0 must hold one row index >= 0 per sequence")
+    row0 = _ragged_row0("lstm_seq_fwd_ragged", lengths, row0)
     _lstm_fwd_operands("lstm_seq_fwd_ragged", "rows", 0, B, hidden, pre, w_hh_t, h_seq, h_last)
-    rows = min(pre.shape[0], h_seq.shape[0])
-    _need(all(r + n <= rows for r, n in zip(row0, lengths)) and rows < 2 ** 31,
-          f"lstm_seq_fwd_ragged: a sequence runs past the {rows} rows of pre / h_seq")
-    end = 0
-    for r, n in sorted(zip(row0, lengths)):
-        _need(r >= end, "lstm_seq_fwd_ragged: two sequences overlap")
-        end = r + n
+    _ragged_inside("lstm_seq_fwd_ragged", lengths, row0, min(pre.shape[0], h_seq.shape[0]), "pre / h_seq")
     d_row0, d_len = _ragged_tables(lengths, row0, pre.device)
     G = lstm_group(hidden)
     steps = sum(max(lengths[i:i + G]) for i in range(0, B, G))  # W_hh is streamed once per step and group
@@ -1125,6 +1136,69 @@ def lstm_seq_fwd_ragged(pre: torch.Tensor, lengths, hidden: int, w_hh_t: torch.T
           "vc_lstm_seq_fwd_ragged", _p(pre), pre.stride(0), B, _p(d_row0), _p(d_len), max(lengths), hidden, _p(w_hh_t),
           _p(h_seq), h_seq.stride(0), _p(h_last), _stream(pre))
     return h_last
+
+
+def lstm_seq_fwd_state(pre: torch.Tensor, lengths, hidden: int, w_hh_t: torch.Tensor, h_seq: torch.Tensor,
+                       h_n: torch.Tensor, c_n: torch.Tensor, h0: torch.Tensor | None = None,
+                       c0: torch.Tensor | None = None, h_all: torch.Tensor | None = None, row0=None,
+                       T: int | None = None) -> tuple:
+    """The inference recurrence with nn.LSTM's state: (h0, c0) f32 [B, H] in (both None: the zero state),
+    (h_n, c_n) f32 [B, H] out; h_n may be h0 and c_n may be c0 (the state updated in place).  Ragged:
+    `lengths` holds one host int >= 0 per sequence and row0 is as in lstm_seq_fwd_ragged; a sequence of
+    length 0 passes its state through.  Dense: lengths=None and T, with B = h_n.shape[0]; sequence b owns
+    rows b*T .. b*T + T - 1.  h_seq bf16 [rows, >= H] as in the other entry points; h_all (optional) f32
+    [rows, >= H] gets the unrounded h of every step.  A sequence run in chunks with the state carried is
+    bit-identical to lstm_seq_fwd / lstm_seq_fwd_ragged on it whole."""
+    name = "lstm_seq_fwd_state"
+    _need(isinstance(h_n, torch.Tensor) and h_n.dim() == 2, f"{name}: h_n f32 [B, H]")
+    B = h_n.shape[0]
+    if lengths is None:
+        _need(T is not None and row0 is None, f"{name}: the dense layout (lengths=None) takes T and no row0")
+        T = int(T)
+        _lstm_shape(B, T, hidden)
+        max_len, min_rows = T, B * T
+    else:
+        lengths = tuple(int(n) for n in lengths)
+        _need(T is None, f"{name}: T belongs to the dense layout (lengths=None)")
+        _need(len(lengths) >= 1 and all(n >= 0 for n in lengths),
+              f"{name}: lengths must be a non-empty sequence of ints >= 0")
+        _need(len(lengths) == B, f"{name}: h_n must hold one row per sequence")
+        max_len, min_rows = max(1, max(lengths)), 0
+        _lstm_shape(B, max_len, hidden)
+        row0 = _ragged_row0(name, lengths, row0)
+    _lstm_fwd_operands(name, "rows", min_rows, B, hidden, pre, w_hh_t, h_seq, h_n)
+    _need((h0 is None) == (c0 is None), f"{name}: h0 and c0 come together (both None: the zero state)")
+    state = [t for t in (h0, c0) if t is not None]
+    _dev(c_n, *state)
+    for t in (h_n, c_n, *state):
+        _need(t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (B, hidden),
+              f"{name}: h0, c0, h_n and c_n are f32 contiguous [B, H]")
+    span = B * hidden * 4
+    for a, b, ok in ((h_n, c_n, False), (h_n, c0, False), (c_n, h0, False), (h_n, h0, True), (c_n, c0, True)):
+        if b is not None and abs(_p(a) - _p(b)) < span:  # overlapping storage: only the exact in-place pairs
+            _need(ok and _p(a) == _p(b), f"{name}: h_n may alias h0 and c_n may alias c0 exactly, nothing else")
+    rows = min(pre.shape[0], h_seq.shape[0])
+    if h_all is not None:
+        _dev(h_all)
+        _need(h_all.dtype == torch.float32 and h_all.dim() == 2 and h_all.shape[0] >= min_rows and
+              h_all.shape[1] >= hidden and h_all.stride(1) == 1, f"{name}: h_all f32 [rows, >= H]")
+        rows = min(rows, h_all.shape[0])
+    G = lstm_group(hidden)
+    if lengths is None:
+        d_row0 = d_len = None
+        group_steps = [T] * -(-B // G)
+    else:
+        _ragged_inside(name, lengths, row0, rows, "pre / h_seq / h_all")
+        d_row0, d_len = _ragged_tables(lengths, row0, pre.device)
+        group_steps = [max(lengths[i:i + G]) for i in range(0, B, G)]
+    # W_hh is streamed once per step and group; from the zero state step 0 has no product
+    steps = sum(n if state else max(n - 1, 0) for n in group_steps)
+    timed("lstm_seq_fwd_state_kernel", "lstm_fwd", 4.0 * hidden * hidden * 4 * steps, "byte", _lib.call,
+          "vc_lstm_seq_fwd_state", _p(pre), pre.stride(0), B, _p(d_row0) if d_row0 is not None else None,
+          _p(d_len) if d_len is not None else None, max_len, hidden, _p(w_hh_t), _p(h0) if state else None,
+          _p(c0) if state else None, _p(h_seq), h_seq.stride(0), _p(h_all) if h_all is not None else None,
+          h_all.stride(0) if h_all is not None else 0, _p(h_n), _p(c_n), _stream(pre))
+    return h_n, c_n
 
 
 def lstm_seq_bwd(gates: torch.Tensor, c_seq: torch.Tensor, B: int, T: int, hidden: int, w_hh: torch.Tensor,

@@ -19,11 +19,16 @@ which keeps bf16 rows for its backward, would cost ~4x the feature error).
 frozen backbone).  The LSTM and the head run as autograd ops over HIP kernels
 (autograd_ops.lstm_layer / mlp_head); dropout masks come from torch's RNG.
 
+Inference beyond the reference: `forward_ragged` batches videos of different lengths, and
+`init_state` / `forward_stream` carry nn.LSTM's (h, c) from call to call (vc_lstm_seq_fwd_state), so a
+recording of any length runs in chunks at bounded memory, with a logit after every frame.
+
 State dict keys are the reference's (resnet50.<child>..., lstm.*, classifier.*).
 """
 from __future__ import annotations
 
 from collections import OrderedDict
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -35,6 +40,12 @@ from .weights import RESNET50_2D, blocks_to_torchvision_resnet50, resnet50_lstm_
     torchvision_resnet50_to_blocks
 
 HEAD_DIM = 64  # classifier.0: Linear(hidden, 64)
+
+
+class LstmState(NamedTuple):
+    """nn.LSTM's (h_n, c_n): f32 [num_layers, B, hidden] each (init_state, forward_stream)."""
+    h: torch.Tensor
+    c: torch.Tensor
 
 
 class VideoResNet50LSTM(torch.nn.Module):
@@ -268,26 +279,94 @@ class VideoResNet50LSTM(torch.nn.Module):
         """Inference: logits f32 [B, 1] (a workspace buffer, overwritten by the next call)."""
         return self._infer(video)
 
-    def _infer(self, x: torch.Tensor, lengths=None) -> torch.Tensor:
+    def _infer(self, x: torch.Tensor, lengths=None, carry=None):
         """The inference path on the frames of x: the backbone, per LSTM layer the projection GEMM over all
         rows and the recurrence (dense over x's B sequences of T frames when lengths is None; else x is
         [1, 3, N, H, W] and the recurrence ragged over `lengths`), then the head.  Returns the workspace's
-        logits buffer."""
+        logits buffer.
+        carry = (state or None, new_state, frame_logits) makes the recurrence the stateful one
+        (vc_lstm_seq_fwd_state): layer l starts from state.h[l] / state.c[l] (None: zeros) and leaves its
+        final state in new_state; the head then runs on the top layer's h_n, and with frame_logits also on
+        the top layer's h of every frame: (logits buffer, frame logits f32 [N, 1] or None) is returned."""
         B, _, T = x.shape[:3]
         nseq = B if lengths is None else len(lengths)
         pk = self._pack(x.device)
         ws = self._workspace(B * T, nseq, x.device)
         inp = self.features(x)
+        hlast, hall = ws["hlast"], None
+        if carry is not None:
+            old, new, frame_logits = carry
+            hlast = new.h[self.layers - 1]
+            if frame_logits:
+                if "hall" not in ws:
+                    ws["hall"] = torch.zeros(ws["pre"].shape[0], self.hidden, dtype=torch.float32, device=x.device)
+                hall = ws["hall"]
         for l, L in enumerate(pk["layers"]):
             hseq = ws["hseq"][l & 1]
             ops.gemm(inp, L["wb"], L["b"], "bias_f32", ws["pre"], op="lstm_ih")
-            if lengths is None:
+            if carry is not None:
+                ops.lstm_seq_fwd_state(ws["pre"], lengths, self.hidden, L["w_hh_t"], hseq, new.h[l], new.c[l],
+                                       h0=None if old is None else old.h[l], c0=None if old is None else old.c[l],
+                                       h_all=hall if l == self.layers - 1 else None)
+            elif lengths is None:
                 ops.lstm_seq_fwd(ws["pre"], B, T, self.hidden, L["w_hh_t"], hseq, ws["hlast"])
             else:
                 ops.lstm_seq_fwd_ragged(ws["pre"], lengths, self.hidden, L["w_hh_t"], hseq, ws["hlast"])
             inp = hseq
         w1, b1, w2, b2 = pk["head"]
-        return ops.mlp_head_fwd(ws["hlast"], w1, b1, w2, b2, ws["logits"])
+        logits = ops.mlp_head_fwd(hlast, w1, b1, w2, b2, ws["logits"])
+        if carry is None:
+            return logits
+        frames = None
+        if hall is not None:  # the same head on the same f32 rows: a sequence's last frame equals its logit
+            frames = ops.mlp_head_fwd(hall[: B * T], w1, b1, w2, b2, torch.empty(B * T, 1, dtype=torch.float32, device=x.device))
+        return logits, frames
+
+    def init_state(self, B: int) -> LstmState:
+        """The zero state of B sequences: h and c f32 [num_layers, B, hidden] on the model's device."""
+        if B < 1:
+            raise ValueError("init_state: B must be >= 1")
+        dev = next(self.parameters()).device
+        z = lambda: torch.zeros(self.layers, B, self.hidden, dtype=torch.float32, device=dev)  # noqa: E731
+        return LstmState(z(), z())
+
+    def forward_stream(self, video: torch.Tensor, lengths, state: LstmState | None = None, frame_logits: bool = False):
+        """Whole-video inference in chunks: `video` f32 [1, 3, N, H, W] holds the NEXT frames of len(lengths)
+        recordings back to back as in forward_ragged (N == sum(lengths) >= 1; a length may be 0: that
+        recording has ended or pauses this round), `state` what the previous call returned (None: the
+        zero state of init_state).  Returns (logits f32 [B, 1], new_state), with frame_logits=True
+        (logits, new_state, f32 [N, 1]): the head on the top layer's h after every frame, in input order.
+        logits[b] is the head on the top layer's h_n[b], so a recording given length 0 keeps its logit,
+        and the last frame's logit of a recording in this call is bit-identical to logits[b].
+        The returned state is NEW tensors: the caller's `state` is left untouched and stays usable (a
+        chunk can be replayed from it).  One backbone pass over the N frames, per layer one projection
+        GEMM and one vc_lstm_seq_fwd_state; memory is bounded by N, not by the recordings' lengths.
+        Eval mode only, as forward_ragged."""
+        if self.training:
+            raise RuntimeError("forward_stream is the inference path: call model.eval() first")
+        if not isinstance(video, torch.Tensor):
+            raise TypeError("video must be a tensor")
+        lengths = tuple(int(n) for n in lengths)
+        if video.dim() != 5 or video.shape[0] != 1 or video.shape[1] != 3:
+            raise ValueError("video must be [1, 3, N, H, W]: the next frames of all videos back to back")
+        if not lengths or min(lengths) < 0 or video.shape[2] < 1 or sum(lengths) != video.shape[2]:
+            raise ValueError(f"lengths {lengths} must be >= 0 and sum to the {video.shape[2]} >= 1 frames of video")
+        if video.device.type != "cuda":
+            raise RuntimeError("VideoResNet50LSTM (vclip_amd) runs on the GPU only: move the clip batch to cuda")
+        B = len(lengths)
+        if state is not None:
+            for t in (state.h, state.c):
+                if not isinstance(t, torch.Tensor) or t.device != video.device or t.dtype != torch.float32 or \
+                        tuple(t.shape) != (self.layers, B, self.hidden) or not t.is_contiguous():
+                    raise ValueError(f"state.h / state.c must be f32 contiguous [{self.layers}, {B}, {self.hidden}] on "
+                                     f"{video.device} (init_state({B}))")
+        x = video.contiguous().float() if video.dtype != torch.float32 else video.contiguous()
+        with torch.no_grad():
+            new = LstmState(torch.empty(self.layers, B, self.hidden, dtype=torch.float32, device=x.device),
+                            torch.empty(self.layers, B, self.hidden, dtype=torch.float32, device=x.device))
+            logits, frames = self._infer(x, lengths, (state, new, frame_logits))
+            logits = logits.clone()  # the workspace buffer is reused by the next call
+        return (logits, new, frames) if frame_logits else (logits, new)
 
     def forward_ragged(self, video: torch.Tensor, lengths) -> torch.Tensor:
         """Batched inference over videos of different lengths: `video` f32 [1, 3, N, H, W] holds the frames of

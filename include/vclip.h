@@ -710,7 +710,33 @@ int vc_lstm_seq_fwd_ragged(const float* pre, int64_t ldpre, int64_t B, const int
                            float* h_last, hipStream_t stream);
 
 /*
- * Its backward through time, t = T-1 .. 0 in one launch, from the saved gates and c_seq.
+ * The stateful inference recurrence, nn.LSTM's (h0, c0) in and (h_n, c_n) out: a recording of any length
+ * runs in chunks with the state carried from call to call, dense or ragged in one entry point.
+ *   row0, len  both NULL: the dense layout of vc_lstm_seq_fwd, sequence b owns rows b*max_len ..
+ *              b*max_len + max_len - 1; both non-NULL: the ragged layout of vc_lstm_seq_fwd_ragged, lengths
+ *              clamped to [0, max_len].  Exactly one NULL is an error.
+ *   h0, c0     f32 [B][hidden], the state before the first step; both NULL = the zero state (step 0 then
+ *              skips the W_hh product like the other entry points).  Exactly one NULL is an error.
+ *   h_n, c_n   f32 [B][hidden], required: the state after each sequence's last step.  A sequence of
+ *              length 0 passes its state through (h_n = h0, c_n = c0, or zeros).  h_n may alias h0 and
+ *              c_n may alias c0 (the in-place update): a workgroup owns its sequences and has read their
+ *              state before its first store.
+ *   h_seq      bf16 (stride ldh), the next layer's GEMM operand, as in the other entry points;
+ *   h_all      optional f32 [rows][hidden] (stride ldha): the unrounded h of every valid step.
+ * A sequence past its end reads no row of pre and writes no row.  Same grouping, slice split, summation
+ * order and cell arithmetic as the other two entry points: run from the zero state it is bit-identical
+ * to them, an explicit all-zero state is bit-identical to the NULL state (finite weights), and a sequence
+ * run in chunks with the state carried is bit-identical (h_seq, final h and c) to the same sequence
+ * run whole.  Deterministic, no atomics.  hidden % 4 == 0, hidden <= 1024; B, max_len >= 1.
+ * Inference only: vc_lstm_seq_bwd takes no initial state.
+ */
+int vc_lstm_seq_fwd_state(const float* pre, int64_t ldpre, int64_t B, const int32_t* row0, const int32_t* len,
+                          int64_t max_len, int64_t hidden, const float* W_hh_t, const float* h0, const float* c0,
+                          uint16_t* h_seq, int64_t ldh, float* h_all, int64_t ldha, float* h_n, float* c_n,
+                          hipStream_t stream);
+
+/*
+ * The backward of vc_lstm_seq_fwd (train variant) through time, t = T-1 .. 0 in one launch, from the saved gates and c_seq.
  *   W_hh    f32 [4*hidden][hidden], natural layout;
  *   dh      last_only = 0: f32 [B*T][hidden] (row b*T + t, stride lddh), dL/d(h_seq);
  *           last_only = 1: f32 [B][hidden] (stride lddh), dL/d(h_last): only step T-1 carries gradient;
