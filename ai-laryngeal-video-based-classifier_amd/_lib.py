@@ -51,6 +51,9 @@ SIGNATURES = {
     "vc_spin": ([c_i64, c_i64, c_p], c_int),
     "vc_cls_init": ([c_p, c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_p], c_int),
     "vc_cls_head": ([c_p, c_i64, c_i64, c_i64, c_i64, c_p, c_p, c_f, c_p, c_p, c_i64, c_p, c_p], c_int),
+    "vc_cls_attention": ([c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_int, c_p, c_i64, c_p, c_i64, c_p], c_int),
+    "vc_skinny_gemm": ([c_p, c_i64, c_p, c_p, c_f, c_p, c_i64, c_i64, c_i64, c_i64, c_p, c_int, c_int, c_p, c_i64,
+                        c_p], c_int),
     "vc_temporal_attention": ([c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_f, c_int, c_p, c_i64, c_p], c_int),
     "vc_window_attention3d": ([c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_int, c_int, c_int, c_int, c_int,
                                c_int, c_p, c_i64, c_p, c_i64, c_p], c_int),

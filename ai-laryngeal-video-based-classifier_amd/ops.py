@@ -391,6 +391,66 @@ def attention(qkv: torch.Tensor, B: int, S: int, H: int, scale: float, out: torc
     return out
 
 
+ATTN_SHORT_MAX_S = 256  # csrc/attention.hip SHORT_MAX_S: up to here `attention` runs the short-sequence kernel
+CLS_ATTN_SPLIT = 256   # include/vclip.h VC_CLS_ATTN_SPLIT: keys per workgroup of vc_cls_attention
+SKINNY_MAX_K = 4096    # include/vclip.h VC_SKINNY_MAX_K
+
+
+def cls_attention_work(B: int, S: int, H: int, device) -> torch.Tensor:
+    """the f32 partials buffer of cls_attention: (max, row sum, o[64]) per (clip, head, key split)"""
+    return torch.zeros(B * H * ((S + CLS_ATTN_SPLIT - 1) // CLS_ATTN_SPLIT) * 66, dtype=torch.float32, device=device)
+
+
+def cls_attention(qkv: torch.Tensor, B: int, S: int, H: int, work: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
+    """The CLS query of each (clip, head) against all S keys: qkv 16-bit [>= B*S, >= 3*H*64] (q|k|v per token
+    row b*S+s, q pre-scaled by scale * log2 e) -> rows b*S of out [>= (B-1)*S + 1, >= H*64], same type.  No
+    row past B*S is read."""
+    _dev(qkv, work, out)
+    _need(qkv.dtype in H16 and out.dtype == qkv.dtype and qkv.stride(1) == 1 and out.stride(1) == 1,
+          "cls_attention dtypes/layout")
+    _need(qkv.shape[1] >= 3 * H * 64 and out.shape[1] >= H * 64, "cls_attention columns")
+    _need(qkv.shape[0] >= B * S and out.shape[0] >= (B - 1) * S + 1, "cls_attention rows")
+    _need(work.dtype == torch.float32 and work.is_contiguous(), "cls_attention work: contiguous f32")
+    _lib.call("vc_cls_attention", _p(qkv), qkv.stride(0), B, S, H, 64, ELEM_F16 if qkv.dtype == torch.float16 else 0,
+              _p(work), work.numel(), _p(out), out.stride(0), _stream(qkv))
+    return out
+
+
+def skinny_gemm_takes(K: int) -> bool:
+    """whether vc_skinny_gemm takes this reduction length"""
+    return K % 8 == 0 and 0 < K <= SKINNY_MAX_K
+
+
+def skinny_gemm(a: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, epilogue: str, out: torch.Tensor,
+                ln: tuple | None = None) -> torch.Tensor:
+    """out[r] (+)= epilogue(a[r] @ w.T + bias) for the few rows of a (any row stride: pass a strided view,
+    e.g. X[:B*S:S] for the CLS rows in place).  w 16-bit [N, K], bias f32 [N]; a [M, K] of w's type, or -- with
+    ln = (gamma, beta, eps) -- f32 rows that are LayerNorm'ed (and rounded to w's type) on the way in.
+    Epilogues: bias / bias_gelu_tanh / bias_gelu_erf (out of w's type) and bias_resid_f32 (f32, in place)."""
+    _dev(a, w, bias, out)
+    M, K = a.shape
+    N = w.shape[0]
+    _need(w.dtype in H16 and w.dim() == 2 and w.shape[1] == K and w.stride(1) == 1 and bias.dtype == torch.float32 and
+          bias.numel() == N and bias.is_contiguous(), "skinny_gemm: w 16-bit [N, K], bias f32 [N]")
+    _need(a.dim() == 2 and a.stride(1) == 1 and out.dim() == 2 and out.stride(1) == 1 and out.shape[0] >= M and
+          out.shape[1] >= N, "skinny_gemm: a [M, K], out [>= M, >= N], unit column strides")
+    _need(epilogue in ("bias", "bias_gelu_tanh", "bias_gelu_erf", "bias_resid_f32"), f"skinny_gemm: epilogue {epilogue}")
+    _need(out.dtype == (torch.float32 if epilogue == "bias_resid_f32" else w.dtype), "skinny_gemm out dtype")
+    if ln is None:
+        _need(a.dtype == w.dtype, "skinny_gemm: a must have w's type")
+        g = b = None
+        eps = 0.0
+    else:
+        g, b, eps = ln
+        _dev(g, b)
+        _need(a.dtype == torch.float32 and g.dtype == torch.float32 and b.dtype == torch.float32 and g.numel() == K and
+              b.numel() == K and g.is_contiguous() and b.is_contiguous(), "skinny_gemm: LayerNorm prologue on f32 rows")
+    _lib.call("vc_skinny_gemm", _p(a), a.stride(0), None if g is None else _p(g), None if b is None else _p(b), eps,
+              _p(w), w.stride(0), M, N, K, _p(bias), EPI[epilogue], ELEM_F16 if w.dtype == torch.float16 else 0, _p(out),
+              out.stride(0), _stream(a))
+    return out
+
+
 def spin(iters: int, device, blocks: int = 1) -> None:
     """`blocks` one-wave workgroups sleeping `iters` x s_sleep 127 each, on the current stream of `device`
     (streams.pick_streams)."""

@@ -159,6 +159,10 @@ class VivitForVideoClassification(torch.nn.Module):
         # with the pixels and all of layer 0 split too, at less than half the extra MFMA work (957 vs 926
         # clips/s, bf16 982: tests/test_fp16_gpu.py, profiles/r05_fp16_clock.json)
         self.precise_ops = ("embed_w", "qkv")
+        # inference only: the last layer's attention, o_proj, LN2, fc1 and fc2 run for the CLS rows alone
+        # (csrc/cls_tail.hip) -- the logits read nothing else of that layer, whose patch tokens are keys and
+        # values only.  False: the full layer (as training, and as a last layer with split operands, always do)
+        self.cls_only_last_layer = True
 
     # ---- state dict in HF naming ---------------------------------------------------
     def hf_state_dict(self):
@@ -385,7 +389,9 @@ class VivitForVideoClassification(torch.nn.Module):
         else:
             Xe = z(Mpad, D, dt=torch.float32)
         ws = dict(A_emb=z(Memb, Kemb), X=Xe[:Mpad], X_emb=Xe, Y=z(Mpad, D),
-                  QKV=z(Mpad, 3 * D), O=z(Mpad, D), Hd=z(Mpad, I), logits=z(B, c.num_labels, dt=torch.float32))
+                  QKV=z(Mpad, 3 * D), O=z(Mpad, D), Hd=z(Mpad, I), logits=z(B, c.num_labels, dt=torch.float32),
+                  # the CLS-only last layer: its attention partials and the CLS rows' MLP hidden state
+                  cls_work=ops.cls_attention_work(B, S, c.num_attention_heads, device), Hc=z(B, I))
         if precise:
             ws["A_emb_split"] = z(Memb, 2 * Kemb)
         self._ws[key] = ws
@@ -434,9 +440,13 @@ class VivitForVideoClassification(torch.nn.Module):
                    tuple(sorted((k, tuple(v) if isinstance(v, list) else v) for k, v in self.gemm_cfg.items())), self.rows,
                    self.precise_layers, tuple(sorted(self.precise_ops)),
                    None if self.split_sizes is None else tuple(self.split_sizes),
-                   None if self.stream_priorities is None else tuple(self.stream_priorities))
+                   None if self.stream_priorities is None else tuple(self.stream_priorities),
+                   self._cls_only())
             return self._graphs.run(key, pix, self._forward_eager, keep=lambda: (self._packed, tuple(self._ws_used)))
         return self._forward_eager(pix)
+
+    def _cls_only(self) -> bool:
+        return bool(self.cls_only_last_layer) and not self.training
 
     def _forward_eager(self, pix: torch.Tensor) -> torch.Tensor:
         self._ws_used = []  # the workspaces this forward addresses (a captured graph keeps exactly these)
@@ -447,7 +457,7 @@ class VivitForVideoClassification(torch.nn.Module):
         self.last_streams = ns
         if ns == 1:
             self.last_split = [B]
-            return self._forward_part(pix, 0)
+            return self._forward_part(pix, 0, cls_only=self._cls_only())
         dev = pix.device
         key = (B, str(dev), "logits")
         if key not in self._ws:
@@ -460,9 +470,11 @@ class VivitForVideoClassification(torch.nn.Module):
         bounds = streams.split_bounds(B, ns, self.split_sizes if self.split_sizes is not None
                                       else SPLIT_DEFAULT.get((B, ns)))
         self.last_split = [bounds[i + 1] - bounds[i] for i in range(ns)]
+        cls_only = self._cls_only()
         if streams.serial():  # instrumentation: the parts one after the other on the caller's stream
             for i in range(ns):
-                self._forward_part(pix[bounds[i]:bounds[i + 1]], i, out=logits[bounds[i]:bounds[i + 1]])
+                self._forward_part(pix[bounds[i]:bounds[i + 1]], i, out=logits[bounds[i]:bounds[i + 1]],
+                                   cls_only=cls_only)
             return logits
         # whole parts enqueued one after the other (measured, tools/exp_streams.py: enqueueing the
         # parts layer by layer round robin ran 725 vs 911 clips/s, chaining their attention launches
@@ -471,7 +483,8 @@ class VivitForVideoClassification(torch.nn.Module):
             for st in sts:
                 pix.record_stream(st)
             streams.fork_parts(sts, cur, [lambda i=i: self._forward_part(pix[bounds[i]:bounds[i + 1]], i,
-                                                                          out=logits[bounds[i]:bounds[i + 1]])
+                                                                          out=logits[bounds[i]:bounds[i + 1]],
+                                                                          cls_only=cls_only)
                                           for i in range(ns)])
 
         # the parts' streams: on different hardware queues, the fastest of several sets timed on the first
@@ -481,7 +494,9 @@ class VivitForVideoClassification(torch.nn.Module):
         go(self._streams)
         return logits
 
-    def _forward_part(self, pix: torch.Tensor, part: int, out=None) -> torch.Tensor:
+    def _forward_part(self, pix: torch.Tensor, part: int, out=None, cls_only: bool = False) -> torch.Tensor:
+        """One part's forward.  cls_only = False: every layer over every token row (X ends as the full last
+        hidden state); True: the last layer past its q|k|v GEMM for the CLS rows only, where it can."""
         c = self.config
         B = pix.shape[0]
         pk = self._pack(pix.device)
@@ -554,7 +569,12 @@ class VivitForVideoClassification(torch.nn.Module):
         (m_qkv, c_qkv), (m_o, c_o), (m_1, c_1), (m_2, c_2) = rows("qkv"), rows("o_proj"), rows("fc1"), rows("fc2")
         Hn = c.num_attention_heads
         attn_flop = 4.0 * S * S * (D // Hn) * Hn * B
-        for L in pk["layers"]:
+        # the last layer for the CLS rows only: not with split operands there, nor at a width the skinny GEMM refuses
+        n_full = len(pk["layers"])
+        if (cls_only and n_full and "split" not in pk["layers"][-1] and D // Hn == 64
+                and ops.skinny_gemm_takes(D) and ops.skinny_gemm_takes(I)):
+            n_full -= 1
+        for li, L in enumerate(pk["layers"]):
             sp = L.get("split", {})  # the split-operand fp16 GEMMs (precise_layers / precise_ops): A wraps against [W_hi | W_lo]
             run("layernorm", tm, "layernorm_kernel", "layernorm", ln_bytes, "byte", ops.layernorm, X, L["ln1_g"],
                 L["ln1_b"], eps, Y, m=m_ln)
@@ -563,6 +583,25 @@ class VivitForVideoClassification(torch.nn.Module):
             else:
                 run("qkv", qkv_gemm, Y, L["w_qkv"], L["b_qkv"], "bias", QKV, m=m_qkv, cfg=c_qkv,
                     flop=2.0 * M * 3 * D * D, op="qkv")
+            if li >= n_full:
+                Xc, Oc, Hc = X[:M:S], O[:M:S], ws["Hc"]  # the CLS rows b*S in place
+                es = Y.element_size()
+                if S <= ops.ATTN_SHORT_MAX_S:
+                    # vc_attention_fwd's short-sequence kernel: one workgroup per (clip, head) with every key in
+                    # LDS, so there is no query work to drop, and its max-free 16-bit P is not what the CLS
+                    # kernel computes (at S = 33 that alone moved the logits by 0.8 of their bf16 error)
+                    run("attention", tm, "attn_fwd_d64_kernel", "attention", attn_flop, "flop", ops.attention, QKV, B,
+                        S, Hn, scale, O, q_prescaled=True)
+                else:
+                    run("cls_attention", tm, "cls_attn_kernel", "cls_attention", B * (2 * S + 2) * D * es, "byte",
+                        ops.cls_attention, QKV, B, S, Hn, ws["cls_work"], O)
+                run("cls_o_proj", tm, "skinny_gemm_kernel", "cls_o_proj", D * D * es, "byte", ops.skinny_gemm, Oc,
+                    L["w_o"], L["b_o"], "bias_resid_f32", Xc)
+                run("cls_fc1", tm, "skinny_gemm_kernel", "cls_fc1", I * D * es, "byte", ops.skinny_gemm, Xc, L["w_1"],
+                    L["b_1"], act, Hc, ln=(L["ln2_g"], L["ln2_b"], eps))
+                run("cls_fc2", tm, "skinny_gemm_kernel", "cls_fc2", D * I * es, "byte", ops.skinny_gemm, Hc, L["w_2"],
+                    L["b_2"], "bias_resid_f32", Xc)
+                continue
             run("attention", tm, "attn_fwd_d64_kernel", "attention", attn_flop, "flop", ops.attention, QKV, B, S, Hn,
                 scale, O, q_prescaled=True)
             if "w_o" in sp:

@@ -227,6 +227,41 @@ int vc_cls_head(const float* x, int64_t ldx, int64_t B, int64_t S, int64_t D,
                 const float* gamma, const float* beta, float eps,
                 const float* Wc, const float* bc, int64_t num_labels, float* logits, hipStream_t stream);
 
+/* ---- The last layer for the CLS rows only (csrc/cls_tail.hip) --------------------------------
+ * The logits read one row per clip (vc_cls_head), so the inference forward runs its last layer's
+ * attention, o_proj, LN2, fc1 and fc2 for the CLS rows alone; the patch tokens of that layer are
+ * keys and values only.  No reference counterpart: the reference runs the full layer
+ * (TF5/.../modeling_vivit.py:229-270) and drops the other rows at the classifier (:556). */
+
+#define VC_CLS_ATTN_SPLIT 256  /* keys per workgroup of vc_cls_attention: a function of nothing but S */
+#define VC_SKINNY_MAX_K 4096   /* vc_skinny_gemm stages 8 rows x K 16-bit values in 64 KB of LDS      */
+
+/*
+ * Attention of the CLS query of each (clip, head) over all S keys, head_dim 64: q = row b*S of the
+ * q columns of qkv (already scaled by softmax scale * log2 e, vc_attention_fwd's q_prescaled),
+ * out[b*S*ldo + h*64 ..] = softmax2(q . K^T) V rounded to `elem`.  Keys are split over
+ * ceil(S / VC_CLS_ATTN_SPLIT) workgroups per (clip, head); each writes (max, row sum, o[64]) fp32
+ * to `work` (work_elems >= B * H * ceil(S / VC_CLS_ATTN_SPLIT) * 66 floats) and a second launch
+ * combines them in split order: no atomics, and a clip's result does not depend on B.  Scores and
+ * P stay fp32; keys past S are masked by index and no row outside [0, B*S) is read.
+ */
+int vc_cls_attention(const uint16_t* qkv, int64_t ld, int64_t B, int64_t S, int64_t H, int64_t head_dim, int elem,
+                     float* work, int64_t work_elems, uint16_t* out, int64_t ldo, hipStream_t stream);
+
+/*
+ * out[r*ldo + n] = epi(A[r*lda ..] . W[n][:] + bias[n]) for M rows at arbitrary row strides (the CLS
+ * rows in place: lda = S * the buffer's row stride), any M (8 rows per workgroup), fp32 accumulation
+ * in an order that depends on K alone.  W is the packed `elem` [N][K] weight of vc_gemm_h16.
+ * A is `elem` [K] per row, or -- with ln_gamma / ln_beta -- fp32 rows that each workgroup
+ * LayerNorms itself (eps, gamma, beta, the statistics and the rounding of the normalised row to
+ * `elem` as vc_layernorm_f32_h16).  Epilogues: VC_EPI_BIAS_BF16 / _GELU_TANH / _GELU_ERF (out `elem`)
+ * and VC_EPI_BIAS_RESID_F32 (out f32, in place; rows not addressed stay untouched).  K % 8 == 0,
+ * K <= VC_SKINNY_MAX_K.  out must not overlap A.
+ */
+int vc_skinny_gemm(const void* A, int64_t lda, const float* ln_gamma, const float* ln_beta, float ln_eps,
+                   const uint16_t* W, int64_t ldw, int64_t M, int64_t N, int64_t K, const float* bias, int epilogue,
+                   int elem, void* out, int64_t ldo, hipStream_t stream);
+
 /* ---- Clip preprocessing ------------------------------------------- */
 
 /*

@@ -28,6 +28,9 @@ ap.add_argument("--gemm-cfg", default=None, help="JSON {op: cfg} override (ViViT
 ap.add_argument("--dtype", default="bf16", choices=("bf16", "fp16", "fp16_precise"),
                 help="ViViT operand type: bench.py's fp16 / fp16_precise legs (compute_dtype, precise_layers = 1)")
 ap.add_argument("--precise-ops", default=None, help="fp16_precise: comma list of split-operand GEMMs (model.precise_ops: embed|embed_w,qkv,o_proj,fc1,fc2)")
+ap.add_argument("--cls-only", type=int, default=1,
+                help="ViViT: 0 runs the last layer in full (model.cls_only_last_layer = False: the forward before "
+                     "csrc/cls_tail.hip)")
 a = ap.parse_args()
 if a.streams is None:
     a.streams = 4 if a.mode == "swin" else 2
@@ -50,6 +53,8 @@ else:
     x = torch.from_numpy(make_synthetic_video(a.batch or 4, 32, 224, seed=1)).cuda()
 if a.gemm_cfg:
     m.gemm_cfg = json.loads(a.gemm_cfg)
+if a.mode == "fwd":
+    m.cls_only_last_layer = bool(a.cls_only)
 if a.dtype != "bf16":
     m.compute_dtype = torch.float16
     m.precise_layers = 1 if a.dtype == "fp16_precise" else 0
