@@ -131,7 +131,11 @@ SIGNATURES = {
     "vc_lstm_seq_fwd_ragged": ([c_p, c_i64, c_i64, c_p, c_p, c_i64, c_i64, c_p, c_p, c_i64, c_p, c_p], c_int),
     "vc_lstm_seq_fwd_state": ([c_p, c_i64, c_i64, c_p, c_p, c_i64, c_i64, c_p, c_p, c_p, c_p, c_i64, c_p, c_i64, c_p, c_p,
                                c_p], c_int),
+    "vc_lstm_seq_fwd_train_state": ([c_p, c_i64, c_i64, c_p, c_p, c_i64, c_i64, c_p, c_p, c_p, c_p, c_p, c_i64, c_p, c_p,
+                                     c_p, c_p, c_p, c_i64, c_p], c_int),
     "vc_lstm_seq_bwd": ([c_p, c_p, c_i64, c_i64, c_i64, c_p, c_p, c_i64, c_int, c_p, c_p, c_p, c_i64, c_p], c_int),
+    "vc_lstm_seq_bwd_state": ([c_p, c_p, c_p, c_i64, c_p, c_p, c_i64, c_i64, c_p, c_p, c_i64, c_p, c_p, c_p, c_p, c_p,
+                               c_i64, c_p, c_p, c_p], c_int),
     "vc_mlp_head_fwd": ([c_p, c_i64, c_i64, c_p, c_p, c_i64, c_p, c_p, c_p, c_i64, c_p, c_p, c_p], c_int),
     "vc_mlp_head_bwd": ([c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_p, c_p, c_p, c_p, c_p, c_p], c_int),
 }

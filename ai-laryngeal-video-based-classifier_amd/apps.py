@@ -541,6 +541,13 @@ LSTM_STREAM_CHUNK_HELP = (
     "writes frame_probabilities/<video>.csv.  128 is the smallest chunk within 5 %% of the best measured rate "
     "(4 videos of 256 frames: 41.0k frames/s at 9.2 GB peak; 32: 36.9k at 2.9 GB; 256: 41.9k at 17.1 GB, "
     "DESIGN.md section 5.11).")
+LSTM_TBPTT_CHUNK_HELP = (
+    "0 (default): off, the reference's training on --sequence_length sampled frames.  N >= 1: training and validation "
+    "use every frame of every video; --batch_size videos advance in lockstep, at most N frames of each per round, "
+    "with the LSTM state carried between rounds and detached (truncated backpropagation through time: one "
+    "backward per round, one optimiser step per batch of videos).  --train_sampling, --val_sampling and "
+    "--sequence_length are ignored for training and validation; the backbone's BatchNorm keeps its running "
+    "statistics.")
 
 
 def build_parser_lstm(inference: bool):
@@ -579,6 +586,8 @@ def build_parser_lstm(inference: bool):
     p.add_argument("--skip_train", action="store_true")
     p.add_argument("--checkpoint_path", type=str, default=None)
     p.add_argument("--num_workers", type=int, default=2)
+    # not in the reference, which trains on --sequence_length sampled frames: truncated BPTT over whole videos
+    p.add_argument("--tbptt_chunk", type=int, default=0, help=LSTM_TBPTT_CHUNK_HELP)
     return p
 
 
@@ -698,23 +707,110 @@ def _lstm_load_state(model, path, logger):
     logger.info(f"Loaded weights from {path}")
 
 
-def _lstm_epoch(model, loader, crit, device, opt, logger, what):
+def _lstm_clip_step(model, batch, crit, device, opt):
+    """The reference's step on one batch of sampled clips (trainer.py:156-170): (logits, labels, loss)."""
+    videos, labels = batch
+    videos, labels = videos.to(device), labels.to(device)
+    if opt is not None:
+        opt.zero_grad()
+    outputs = model(videos)
+    loss = crit(outputs, labels.unsqueeze(1))
+    if opt is not None:
+        loss.backward()
+        opt.step()
+    return outputs.detach(), labels, loss.item()
+
+
+def _lstm_tbptt_rounds(frame_counts, chunk):
+    """Rounds in which each video is live when videos of `frame_counts` frames advance <= chunk frames per round."""
+    chunk = int(chunk)
+    if chunk < 1:
+        raise ValueError("chunk must be >= 1")
+    rounds = [-(-int(n) // chunk) for n in frame_counts]
+    if not rounds or min(rounds) < 0 or max(rounds) == 0:
+        raise ValueError(f"no frames to train on: frame counts {list(frame_counts)}")
+    return rounds
+
+
+def lstm_tbptt_pairs(frame_counts, chunk) -> int:
+    """The (video, round) pairs of a batch, P = sum_v ceil(frames_v / chunk): video v is live in rounds
+    0 .. ceil(frames_v / chunk) - 1.  Known from the frame counts before the first frame is read."""
+    return sum(_lstm_tbptt_rounds(frame_counts, chunk))
+
+
+def lstm_tbptt_round_weights(frame_counts, chunk):
+    """The weight of each round's loss: every (video, round) pair weighs 1 / P (lstm_tbptt_pairs).  The
+    criterion averages over a round's live videos, so times live / P it becomes that round's share of the mean
+    over all P pairs: the weights add up to 1 and the batch loss keeps the scale of the default trainer's,
+    whatever the lengths.  Returns one weight per round, the longest video's rounds."""
+    rounds = _lstm_tbptt_rounds(frame_counts, chunk)
+    pairs = sum(rounds)
+    return [sum(1 for r in rounds if r > k) / pairs for k in range(max(rounds))]
+
+
+class LstmWholeVideoBatches:
+    """The --tbptt_chunk loader: batches ([paths], [labels]) of `batch_size` whole videos of a VideoDataset,
+    a short last batch dropped as the default train / val loaders do.  shuffle: a new permutation of the
+    dataset's video_paths per pass, seeded by (LSTM_SEED, pass number)."""
+
+    def __init__(self, dataset, batch_size, shuffle):
+        self.paths, self.labels = list(dataset.video_paths), list(dataset.labels)
+        self.batch_size, self.shuffle, self.epoch = int(batch_size), shuffle, 0
+
+    def __len__(self):
+        return len(self.paths) // self.batch_size
+
+    def __iter__(self):
+        order = list(range(len(self.paths)))
+        if self.shuffle:
+            order = [int(i) for i in np.random.RandomState([LSTM_SEED, self.epoch]).permutation(len(order))]
+            self.epoch += 1
+        for k in range(len(self)):
+            idx = order[k * self.batch_size:(k + 1) * self.batch_size]
+            yield [self.paths[i] for i in idx], [self.labels[i] for i in idx]
+
+
+def lstm_tbptt_step(chunk):
+    """The step of `_lstm_epoch` for --tbptt_chunk: one batch of whole videos in rounds of <= chunk frames.
+    With `opt`: forward_train_stream from the carried, detached state, the criterion on the videos live in the round
+    times its lstm_tbptt_round_weights share, backward() per round (the round's graph is freed there), one
+    opt.step() per batch.  Without: forward_stream over the same rounds.  Returns (each video's logit after
+    its own last frame, labels, the criterion on those logits), which the epoch's loss and AUROC are made of."""
+    def step(model, batch, crit, device, opt):
+        paths, labels = batch
+        sources = [video_io.open_video(p) for p in paths]
+        weights = lstm_tbptt_round_weights([s.total_frames for s in sources], chunk)
+        labels = torch.tensor(labels, dtype=torch.float32, device=device)
+        final = torch.zeros(len(paths), 1, dtype=torch.float32, device=device)
+        if opt is not None:
+            opt.zero_grad()
+        state = None
+        for w, (clip, lens) in zip(weights, lstm_stream_rounds(sources, chunk, device)):
+            live = torch.tensor([b for b, n in enumerate(lens) if n], device=device)
+            if opt is not None:
+                logits, state = model.forward_train_stream(clip, lens, state)
+                (crit(logits[live], labels[live].unsqueeze(1)) * w).backward()
+                state = state.detach()
+            else:
+                logits, state = model.forward_stream(clip, lens, state)
+            final[live] = logits.detach()[live]
+        if opt is not None:
+            opt.step()
+        return final, labels, crit(final, labels.unsqueeze(1)).item()
+    return step
+
+
+def _lstm_epoch(model, loader, crit, device, opt, logger, what, step=_lstm_clip_step):
     """One pass over a loader (trainer.py:146-199 with `opt`, :202-249 without): (loss, acc, auroc, number of
-    videos seen).  A failing batch is logged and skipped."""
+    videos seen).  `step` runs one batch and returns (logits, labels, loss).  A failing batch is logged and
+    skipped."""
     from sklearn.metrics import accuracy_score
     total, scores, labels_all = 0.0, [], []
-    for videos, labels in loader:
+    for batch in loader:
         try:
-            videos, labels = videos.to(device), labels.to(device)
-            if opt is not None:
-                opt.zero_grad()
-            outputs = model(videos)
-            loss = crit(outputs, labels.unsqueeze(1))
-            if opt is not None:
-                loss.backward()
-                opt.step()
-            total += loss.item() * videos.size(0)
-            scores.extend(torch.sigmoid(outputs.detach()).float().cpu().numpy().reshape(-1))
+            outputs, labels, loss = step(model, batch, crit, device, opt)
+            total += loss * labels.numel()
+            scores.extend(torch.sigmoid(outputs).float().cpu().numpy().reshape(-1))
             labels_all.extend(labels.cpu().numpy().reshape(-1))
         except Exception as e:  # noqa: BLE001
             logger.error(f"Error in {what} batch: {str(e)}")
@@ -754,8 +850,9 @@ def evaluate_lstm(model, loader, device, exp_dir, logger, class_names=None):
     return m
 
 
-def train_lstm(model, loaders, labels, device, config, exp_dir, logger):
-    """trainer.py:124-398 without wandb and the plots: returns (history, best model path or None)."""
+def train_lstm(model, loaders, labels, device, config, exp_dir, logger, step=_lstm_clip_step):
+    """trainer.py:124-398 without wandb and the plots: returns (history, best model path or None).  `step` is
+    `_lstm_epoch`'s: the reference's step on sampled clips, or lstm_tbptt_step(chunk) on LstmWholeVideoBatches."""
     from .optim import AdamW
     exp_dir = Path(exp_dir)
     pos_weight = torch.tensor([lstm_pos_weight(labels)], dtype=torch.float32, device=device)
@@ -772,10 +869,10 @@ def train_lstm(model, loaders, labels, device, config, exp_dir, logger):
     best_path = Path(config["model_dir"]) / f"model_{datetime.now().strftime('%Y%m%d_%H%M%S')}.pth"
     for epoch in range(config["epochs"]):
         model.train()
-        tr_loss, tr_acc, tr_auroc, tn = _lstm_epoch(model, loaders["train"], crit, device, opt, logger, "training")
+        tr_loss, tr_acc, tr_auroc, tn = _lstm_epoch(model, loaders["train"], crit, device, opt, logger, "training", step)
         model.eval()
         with torch.no_grad():
-            va_loss, va_acc, va_auroc, vn = _lstm_epoch(model, loaders["val"], crit, device, None, logger, "validation")
+            va_loss, va_acc, va_auroc, vn = _lstm_epoch(model, loaders["val"], crit, device, None, logger, "validation", step)
         # a failing batch is logged and skipped, but an epoch in which EVERY batch failed must not go on to
         # save a "best" model (as run_main)
         if tn == 0:
@@ -809,9 +906,13 @@ def train_lstm(model, loaders, labels, device, config, exp_dir, logger):
 
 
 def run_main_lstm(argv=None):
-    """resnet50-2d-lstm/main.py: returns (test metrics or None, history, experiment dir)."""
+    """resnet50-2d-lstm/main.py: returns (test metrics or None, history, experiment dir).  With --tbptt_chunk N >= 1
+    training and validation run on whole videos in rounds of <= N frames (LstmWholeVideoBatches, lstm_tbptt_step:
+    truncated BPTT with the LSTM state carried); the rest of the run is the same code."""
     import os
     args = build_parser_lstm(inference=False).parse_args(argv)
+    if args.tbptt_chunk < 0:
+        raise ValueError("--tbptt_chunk must be >= 0 (0: off)")
     random.seed(LSTM_SEED)  # src/utils/logging_utils.py set_seed(SEED)
     np.random.seed(LSTM_SEED)
     torch.manual_seed(LSTM_SEED)
@@ -824,7 +925,7 @@ def run_main_lstm(argv=None):
     test_dir = args.test_dir if args.test_dir else args.data_dir
     config = {k: getattr(args, k) for k in ("data_dir", "model_dir", "train_sampling", "val_sampling", "test_sampling",
                                             "loss_weight", "learning_rate", "batch_size", "epochs", "patience",
-                                            "hidden_size", "num_layers", "dropout", "sequence_length")}
+                                            "hidden_size", "num_layers", "dropout", "sequence_length", "tbptt_chunk")}
     config.update(test_dir=test_dir, log_dir=exp.get_experiment_dir())
     device = _device()
     logger.info(f"Using device: {device}")
@@ -842,8 +943,18 @@ def run_main_lstm(argv=None):
         _lstm_load_state(model, args.checkpoint_path, logger)
         best_path = args.checkpoint_path
     elif train:
+        step = _lstm_clip_step
+        if args.tbptt_chunk:
+            logger.info(f"--tbptt_chunk {args.tbptt_chunk}: training and validation use every frame of every video, "
+                        "--train_sampling, --val_sampling and --sequence_length are ignored for them")
+            # a round holds a handful of videos: batch statistics would drift the running ones round by round
+            model.freeze_backbone_bn = True
+            logger.info("--tbptt_chunk: freeze_backbone_bn = True, the backbone's BatchNorm keeps its running statistics")
+            loaders = dict(loaders, train=LstmWholeVideoBatches(datasets["train"], args.batch_size, shuffle=True),
+                           val=LstmWholeVideoBatches(datasets["val"], args.batch_size, shuffle=False))
+            step = lstm_tbptt_step(args.tbptt_chunk)
         history, best_path = train_lstm(model, loaders, datasets["train"].labels, device, config,
-                                        exp.get_experiment_dir(), logger)
+                                        exp.get_experiment_dir(), logger, step)
         logger.info(f"Training completed. Best model saved to {best_path}")
     else:
         logger.info("Skipping training as requested")
@@ -903,16 +1014,14 @@ def _lstm_load_video(path, method, sequence_length, device):
     return pp.lstm_inference_preprocess(frames), idx, total
 
 
-def lstm_stream_videos(model, sources, chunk, device):
-    """Whole-video inference over opened videos (video_io sources) in lockstep: every round reads the next
-    <= chunk frames of each, resizes and normalises them on the GPU as _lstm_load_video does, and makes one
-    forward_stream call with the carried state; a finished video takes length 0 and keeps its logit.
-    Returns (probabilities, one per video; per-frame probability lists, total_frames entries each)."""
+def lstm_stream_rounds(sources, chunk, device):
+    """Opened videos (video_io sources) in lockstep: every round reads the next <= chunk frames of each, resizes
+    and normalises them on the GPU as _lstm_load_video does, and yields (clip f32 [1, 3, N, 224, 224], the
+    frames of each video in it); a finished video takes length 0.  The layout of forward_stream and
+    forward_train_stream."""
     from . import preprocess as pp
     totals = [int(s.total_frames) for s in sources]
     pos = [0] * len(sources)
-    frame_probs = [[] for _ in sources]
-    state, logits = None, None
     while any(p < t for p, t in zip(pos, totals)):
         lens = [min(chunk, t - p) for p, t in zip(pos, totals)]
         parts = [np.ascontiguousarray(s.read(list(range(p, p + n)))) for s, p, n in zip(sources, pos, lens) if n]
@@ -921,13 +1030,23 @@ def lstm_stream_videos(model, sources, chunk, device):
             frames = pp.cv2_resize_u8(torch.from_numpy(np.concatenate(parts)).to(device), (224, 224))
         else:
             frames = torch.cat([pp.cv2_resize_u8(torch.from_numpy(a).to(device), (224, 224)) for a in parts])
-        logits, state, fl = model.forward_stream(pp.lstm_inference_preprocess(frames), lens, state, frame_logits=True)
+        pos = [p + n for p, n in zip(pos, lens)]
+        yield pp.lstm_inference_preprocess(frames), lens
+
+
+def lstm_stream_videos(model, sources, chunk, device):
+    """Whole-video inference over opened videos in lockstep (lstm_stream_rounds): one forward_stream call per
+    round with the carried state; a finished video keeps its logit.
+    Returns (probabilities, one per video; per-frame probability lists, total_frames entries each)."""
+    frame_probs = [[] for _ in sources]
+    state, logits = None, None
+    for clip, lens in lstm_stream_rounds(sources, chunk, device):
+        logits, state, fl = model.forward_stream(clip, lens, state, frame_logits=True)
         fp = torch.sigmoid(fl.float()).reshape(-1).tolist()
         at = 0
         for b, n in enumerate(lens):
             frame_probs[b].extend(fp[at:at + n])
             at += n
-            pos[b] += n
     return torch.sigmoid(logits.float()).reshape(-1).tolist(), frame_probs
 
 

@@ -24,6 +24,9 @@ Every arithmetic op here is a HIP kernel of libvclip.so, forward and backward:
               with b_ih + b_hh fused, the fp32 recurrence vc_lstm_seq_fwd (train variant: gates, c and
               bf16 h_prev saved; optional inter-layer dropout mask on the stored h_seq), backward
               vc_lstm_seq_bwd (BPTT) + vc_wgrad_bf16 (dW_ih, dW_hh) + vc_colsum (db) + the dgrad GEMM (dx);
+  lstm_layer_state  the same layer from a state (h0, c0) over sequences of different lengths, (h_n, c_n) out and
+              differentiable like h_seq: vc_lstm_seq_fwd_train_state / vc_lstm_seq_bwd_state (dh0, dc0), the
+              GEMMs, wgrad and colsum of lstm_layer; chunks of whole videos chain through the state;
   mlp_head    Linear -> ReLU -> Dropout -> Linear in fp32, vc_mlp_head_fwd / vc_mlp_head_bwd.
 The tensors between them (residual adds, the clip <-> frame permutes, the CLS frame mean) are
 ordinary torch tensor ops: layout glue, autograd's bookkeeping.  Rows are padded internally to the
@@ -617,6 +620,100 @@ def lstm_layer(x, w_ih, w_hh, b_ih, b_hh, B, T, keep=None, last_only=False, need
     need_dx=False skips the input gradient (layer 0 behind a frozen backbone).  The input gradient
     has x's dtype.  packed: pack_lstm_weights(w_ih, w_hh) kept by the caller.  hidden % 4 == 0, <= 1024."""
     return _LstmLayer.apply(x, w_ih, w_hh, b_ih, b_hh, B, T, keep, last_only, need_dx, packed)
+
+
+class _LstmLayerState(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, w_ih, w_hh, b_ih, b_hh, h0, c0, layout, keep, need_dx: bool, packed):
+        lengths, B, T = layout  # ragged: (lengths, B, None); dense: (None, B, T)
+        M, Din = x.shape
+        want = B * T if lengths is None else sum(lengths)
+        if M != want or M < 1:
+            raise _lib.VclipError(f"lstm_layer_state: x has {M} rows, the sequences hold {want} (>= 1) in all")
+        H = w_hh.shape[1]
+        if tuple(w_hh.shape) != (4 * H, H) or tuple(w_ih.shape) != (4 * H, Din):
+            raise _lib.VclipError("lstm_layer_state: w_ih [4H, Din], w_hh [4H, H]")
+        if (h0 is None) != (c0 is None):
+            raise _lib.VclipError("lstm_layer_state: h0 and c0 come together (both None: the zero state)")
+        pk = packed if packed is not None else pack_lstm_weights(w_ih, w_hh)
+        Np, Kp = pk["wb"].shape
+        Mp, Hp = _round_up(M, 256), _round_up(H, 128)
+        dev = x.device
+        xp = _as_operand(x.detach(), Mp, Kp)
+        bb = torch.zeros(Np, dtype=torch.float32, device=dev)
+        bb[: 4 * H] = b_ih.detach().float() + b_hh.detach().float()
+        pre = torch.empty(Mp, Np, dtype=torch.float32, device=dev)
+        ops.gemm(xp, pk["wb"], bb, "bias_f32", pre, op="lstm_ih")
+        h_seq = torch.zeros(Mp, Hp, dtype=torch.bfloat16, device=dev)
+        h_prev = torch.zeros(Mp, Hp, dtype=torch.bfloat16, device=dev)
+        h_n = torch.empty(B, H, dtype=torch.float32, device=dev)
+        c_n = torch.empty(B, H, dtype=torch.float32, device=dev)
+        gates = torch.empty(M, 4 * H, dtype=torch.float32, device=dev)
+        c_seq = torch.empty(M, H, dtype=torch.float32, device=dev)
+        kp = None if keep is None else keep.detach().float().contiguous().view(M, H)
+        h0c = None if h0 is None else h0.detach().float().contiguous()
+        c0c = None if c0 is None else c0.detach().float().contiguous()
+        ops.lstm_seq_fwd_train_state(pre, lengths, H, pk["w_hh_t"], h_seq, h_n, c_n, gates, c_seq, h_prev, h0=h0c, c0=c0c,
+                                     keep=kp, T=T)
+        opt = [t for t in (c0c, kp) if t is not None]
+        ctx.save_for_backward(xp, h_prev, gates, c_seq, pk["wt"], pk["w_hh"], *opt)
+        ctx.dims = (lengths, B, T, H, Din, need_dx, x.dtype, c0c is not None, kp is not None)
+        ctx.set_materialize_grads(False)
+        return h_seq[:M, :H], h_n, c_n
+
+    @staticmethod
+    def backward(ctx, dh_seq, dh_n, dc_n):
+        xp, h_prev, gates, c_seq, wt, w_hh = ctx.saved_tensors[:6]
+        lengths, B, T, H, Din, need_dx, xdtype, has_state, has_keep = ctx.dims
+        opt = list(ctx.saved_tensors[6:])
+        c0c = opt.pop(0) if has_state else None
+        kp = opt.pop(0) if has_keep else None
+        M = gates.shape[0]
+        Mp, Kp = xp.shape
+        Np, Hp = wt.shape[1], h_prev.shape[1]
+        dev = xp.device
+        f = lambda t: None if t is None else t.float().contiguous()  # noqa: E731
+        dpre = torch.empty(M, 4 * H, dtype=torch.float32, device=dev)
+        dpb = torch.zeros(Mp, Np, dtype=torch.bfloat16, device=dev)
+        dh0 = dc0 = None
+        if has_state and (ctx.needs_input_grad[5] or ctx.needs_input_grad[6]):
+            dh0 = torch.empty(B, H, dtype=torch.float32, device=dev)
+            dc0 = torch.empty(B, H, dtype=torch.float32, device=dev)
+        ops.lstm_seq_bwd_state(gates, c_seq, B, lengths, H, w_hh, dpre, dpb, dh_seq=f(dh_seq), dh_n=f(dh_n), dc_n=f(dc_n),
+                               c0=c0c, keep=kp, dh0=dh0, dc0=dc0, T=T)
+        dw_ih = torch.empty(Np, Kp, dtype=torch.float32, device=dev)
+        ops.wgrad(dpb, xp, dw_ih, ops.wgrad_work(Mp, Np, Kp, dev))
+        dw_hh = torch.empty(Np, Hp, dtype=torch.float32, device=dev)
+        ops.wgrad(dpb, h_prev, dw_hh, ops.wgrad_work(Mp, Np, Hp, dev))
+        db = torch.empty(4 * H, dtype=torch.float32, device=dev)
+        ops.colsum(dpre, db, ops.colsum_work(M, 4 * H, dev), m=M)
+        dx = None
+        if need_dx:
+            dxp = torch.empty(Mp, Kp, dtype=torch.float32, device=dev)
+            ops.gemm(dpb, wt, _zeros_f32(Kp, dev), "bias_f32", dxp, op="lstm_dx")
+            dx = dxp[:M, :Din].to(xdtype)
+        return (dx, dw_ih[: 4 * H, :Din], dw_hh[: 4 * H, :H], db, db.clone(), dh0 if ctx.needs_input_grad[5] else None,
+                dc0 if ctx.needs_input_grad[6] else None, None, None, None, None)
+
+
+def lstm_layer_state(x, w_ih, w_hh, b_ih, b_hh, lengths_or_BT, h0=None, c0=None, keep=None, need_dx=True, packed=None):
+    """lstm_layer with nn.LSTM's state and sequences of different lengths: one layer over x bf16 [rows, Din]
+    from (h0, c0) f32 [B, H] (both None: the zero state) -> (h_seq bf16 [rows, H], h_n f32 [B, H], c_n f32
+    [B, H]).  lengths_or_BT is a sequence of host ints >= 0, one per sequence, whose rows lie back to back in
+    x (rows = their sum >= 1; a sequence of length 0 passes its state through), or the pair (B, T) as a
+    tuple for the dense rows b*T + t.  keep f32 [rows, H] scales h_seq only; h_n and c_n are never masked.
+    Gradients flow from h_seq, h_n and c_n in any combination, mask or not, to x (need_dx), the weights,
+    the biases and, where they require grad, h0 and c0: chunks of a long sequence chained through their
+    states backpropagate through time across the chunk boundaries, and detaching the state between chunks
+    truncates it there.  dW_hh includes each sequence's first step through bf16(h0)."""
+    if isinstance(lengths_or_BT, tuple):
+        if len(lengths_or_BT) != 2:
+            raise _lib.VclipError("lstm_layer_state: a tuple is the dense (B, T); pass ragged lengths as a list")
+        layout = (None, int(lengths_or_BT[0]), int(lengths_or_BT[1]))
+    else:
+        lengths = tuple(int(n) for n in lengths_or_BT)
+        layout = (lengths, len(lengths), None)
+    return _LstmLayerState.apply(x, w_ih, w_hh, b_ih, b_hh, h0, c0, layout, keep, need_dx, packed)
 
 
 class _MlpHead(torch.autograd.Function):

@@ -4,11 +4,13 @@
 // split-K wgrad GEMMs) and the Linear -> ReLU -> Dropout -> Linear head, forward and backward.
 //
 // There are two recurrence kernels, one forward and one backward.  The forward one is a template over
-// <G, RAGGED, STATE>: dense inference, dense train (gates != nullptr), the ragged inference over
-// sequences of different lengths and the stateful inference ((h0, c0) in, (h_n, c_n) out) are
-// instantiations of one step loop, so a sequence comes out bit-identical whichever entry ran it.  Both kernels share one schedule, whose launch geometry the
-// host keeps in SeqLaunch.  A workgroup owns G whole sequences (G = 4 for
-// hidden <= 512, else 2) from the first step to the last, so there is no cross-workgroup barrier.
+// <G, RAGGED, STATE, TRAIN>: dense inference, dense train (gates != nullptr), the ragged inference over
+// sequences of different lengths, the stateful inference ((h0, c0) in, (h_n, c_n) out) and the stateful
+// train variant are instantiations of one step loop, so a sequence comes out bit-identical whichever
+// entry ran it.  The backward one is a template over <G, STATE>: BPTT from the zero state over dense rows,
+// and BPTT over dense or ragged rows with c0 in and (dh0, dc0) out, again one step loop.  Both kernels
+// share one schedule, whose launch geometry the host keeps in SeqLaunch.  A workgroup owns G whole sequences
+// (G = 4 for hidden <= 512, else 2) from the first step to the last, so there is no cross-workgroup barrier.
 // HP = hidden rounded up to 64; the block has S * HP threads, S = 1024 / HP.  Thread (s, j) owns
 // hidden unit j and slice s of the reduction (forward: the k range of h_{t-1}; backward: the row
 // range of the 4H gate gradients).  Lanes run over j, so every W_hh read is a contiguous row piece:
@@ -106,7 +108,10 @@ __global__ void __launch_bounds__(256) video_to_cl_h16_kernel(const float* __res
 // unrounded h of every step.  hfin may alias h0 and cfin c0: the workgroup owns its sequences and has h0
 // in LDS and c0 in registers before its first store, so these four carry no __restrict__.  hlast is
 // not touched.  STATE = false compiles all of it out.
-template <int G, bool RAGGED, bool STATE = false>
+// Stateful train (TRAIN = true, with STATE = true): gates, cseq and hprev are written as in the dense train
+// variant and keep scales the stored h_seq, all indexed by the sequence's own rows; hprev of a first step
+// is bf16(h0[b]) (zero without a state), the operand of the W_hh gradient.  hall is not used.
+template <int G, bool RAGGED, bool STATE = false, bool TRAIN = false>
 __global__ void __launch_bounds__(kMaxThreads)
 lstm_seq_fwd_kernel(const float* __restrict__ pre, int64_t ldpre, int B, int T, int H, const float* __restrict__ WT,
                     const int32_t* __restrict__ row0, const int32_t* __restrict__ len, const float* __restrict__ keep,
@@ -114,6 +119,7 @@ lstm_seq_fwd_kernel(const float* __restrict__ pre, int64_t ldpre, int B, int T, 
                     float* __restrict__ cseq, uint16_t* __restrict__ hprev, int64_t ldhp, const float* h0, const float* c0,
                     float* hfin, float* cfin, float* __restrict__ hall, int64_t ldha) {
     static_assert(RAGGED || !STATE, "the stateful instantiations are the ragged ones");
+    static_assert(STATE || !TRAIN, "TRAIN marks the stateful train variant; the dense one is RAGGED = false with gates");
     extern __shared__ __align__(16) float smem[];
     const int HP = (H + 63) & ~63;
     const int S = kMaxThreads / HP;
@@ -241,8 +247,8 @@ lstm_seq_fwd_kernel(const float* __restrict__ pre, int64_t ldpre, int B, int T, 
                 c[g] = __builtin_fmaf(fg, c[g], ig * gg);
                 const float hn = og * tanhf_(c[g]);
                 hl[(size_t)j * G + g] = hn;
-                float hs = hn;  // what h_seq keeps: times keep in the dense train step
-                if constexpr (!RAGGED) hs *= keep ? keep[row * H + j] : 1.0f;
+                float hs = hn;  // what h_seq keeps: times keep in the train steps
+                if constexpr (!RAGGED || TRAIN) hs *= keep ? keep[row * H + j] : 1.0f;
                 hseq[row * ldh + j] = f2bf(hs);
                 if constexpr (STATE) {
                     if (hall) hall[row * ldha + j] = hn;
@@ -253,7 +259,7 @@ lstm_seq_fwd_kernel(const float* __restrict__ pre, int64_t ldpre, int B, int T, 
                 } else {
                     if (t == ln[g] - 1) hlast[(int64_t)(b0 + g) * H + j] = hn;
                 }
-                if constexpr (!RAGGED) {
+                if constexpr (!RAGGED || TRAIN) {
                     if (gates) {
                         float* gp = gates + row * H4 + j;
                         gp[0] = ig;
@@ -273,11 +279,24 @@ lstm_seq_fwd_kernel(const float* __restrict__ pre, int64_t ldpre, int B, int T, 
 // BPTT, t = T-1 .. 0, from the saved gates and c.  dh: last_only = 0: [B*T][H] rows b*T + t;
 // last_only = 1: [B][H], the gradient of the last step's h only.  keep (optional) scales the incoming
 // dh rows like the forward scaled the stored h_seq.  W = W_hh [4H][H].  Writes dpre fp32 and bf16.
-template <int G>
+// Stateful (STATE = true): the backward of the stateful train forward.  Rows as there (row0 == nullptr: the
+// dense rows b * T + t; else q0 = row0[b], ln = len[b] clamped to [0, T = max_len]).  The workgroup loops
+// from the largest length of its group down to 0 (uniform: the barriers stay legal), so every sequence
+// reaches its step 0 in the last pass; one that has not started yet (t >= ln) leaves its zero rows in the
+// LDS dpre tile and touches no memory.  dh = dL/dh_seq rows (optional, times keep), last_only is not read;
+// dhn / dcn (optional, [B][H], never masked) enter at a sequence's last valid step in place of the
+// recurrent dh / the carried dc, which are zero there; c0 (optional) is the c_{-1} of step 0.  With dh0 /
+// dc0 the W_hh^T product runs once more after step 0 on the same tile: dh0 = W_hh^T dpre_0, dc0 = dc_0 f_0,
+// and a sequence of length 0 passes dhn / dcn (or zeros) through.  dh0 may alias dhn and dc0 dcn: the
+// one thread that writes an element is the one that read it, so these four carry no __restrict__.
+// STATE = false compiles all of it out.
+template <int G, bool STATE = false>
 __global__ void __launch_bounds__(kMaxThreads)
 lstm_seq_bwd_kernel(const float* __restrict__ gates, const float* __restrict__ cseq, int B, int T, int H,
                     const float* __restrict__ W, const float* __restrict__ dh, int64_t lddh, int last_only,
-                    const float* __restrict__ keep, float* __restrict__ dpre, uint16_t* __restrict__ dpreb, int64_t lddb) {
+                    const float* __restrict__ keep, float* __restrict__ dpre, uint16_t* __restrict__ dpreb, int64_t lddb,
+                    const int32_t* __restrict__ row0, const int32_t* __restrict__ len, const float* __restrict__ c0,
+                    const float* dhn, const float* dcn, float* dh0, float* dc0) {
     extern __shared__ __align__(16) float smem[];
     const int HP = (H + 63) & ~63;
     const int S = kMaxThreads / HP;
@@ -298,16 +317,35 @@ lstm_seq_bwd_kernel(const float* __restrict__ gates, const float* __restrict__ c
     for (int i = threadIdx.x; i < R * G; i += blockDim.x) dl[i] = 0.f;  // rows of absent sequences stay 0
     __syncthreads();
 
-    for (int t = T - 1; t >= 0; --t) {
+    int64_t q0[G];  // STATE: the first row and the length of each sequence, uniform over the workgroup
+    int ln[G];
+    int steps = T;
+    if constexpr (STATE) {
+        steps = 0;
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+            q0[g] = row0 ? (g < nb ? row0[b0 + g] : 0) : (int64_t)(b0 + g) * T;
+            ln[g] = g < nb ? (row0 ? min(max(len[b0 + g], 0), T) : T) : 0;
+            steps = max(steps, ln[g]);
+        }
+    }
+
+    for (int t = steps - 1; t >= 0; --t) {
         if (s == 0 && unit) {
 #pragma unroll
             for (int g = 0; g < G; ++g) {
-                if (g >= nb) {
+                if (STATE ? t >= ln[g] : g >= nb) {  // an absent sequence, or one that has not started yet
                     continue;
                 }
-                const int64_t row = (int64_t)(b0 + g) * T + t;
+                const int64_t row = STATE ? q0[g] + t : (int64_t)(b0 + g) * T + t;
                 float dht = dhr[g];
-                if (!last_only) {
+                if constexpr (STATE) {
+                    if (t == ln[g] - 1) {  // the last valid step: the gradients of the outgoing state come in
+                        dht = dhn ? dhn[(int64_t)(b0 + g) * H + j] : 0.f;
+                        dc[g] = dcn ? dcn[(int64_t)(b0 + g) * H + j] : 0.f;
+                    }
+                    if (dh) dht += dh[row * lddh + j] * (keep ? keep[row * H + j] : 1.0f);
+                } else if (!last_only) {
                     dht += dh[row * lddh + j] * (keep ? keep[row * H + j] : 1.0f);
                 } else if (t == T - 1) {
                     dht += dh[(int64_t)(b0 + g) * lddh + j] * (keep ? keep[row * H + j] : 1.0f);
@@ -315,7 +353,10 @@ lstm_seq_bwd_kernel(const float* __restrict__ gates, const float* __restrict__ c
                 const float* gp = gates + row * H4 + j;
                 const float ig = gp[0], fg = gp[H], gg = gp[2 * (int64_t)H], og = gp[3 * (int64_t)H];
                 const float ct = cseq[row * H + j];
-                const float cp = t > 0 ? cseq[(row - 1) * H + j] : 0.f;
+                float cp = t > 0 ? cseq[(row - 1) * H + j] : 0.f;
+                if constexpr (STATE) {
+                    if (t == 0 && c0) cp = c0[(int64_t)(b0 + g) * H + j];
+                }
                 const float tc = tanhf_(ct);
                 const float dct = dht * og * (1.0f - tc * tc) + dc[g];
                 const float d_i = dct * gg * ig * (1.0f - ig);
@@ -339,8 +380,8 @@ lstm_seq_bwd_kernel(const float* __restrict__ gates, const float* __restrict__ c
                 db[3 * (int64_t)H] = f2bf(d_o);
             }
         }
-        if (t == 0) break;  // uniform: nothing consumes dh_{-1}
-        __syncthreads();    // dpre_t of the group in LDS
+        if (t == 0 && !(STATE && dh0)) break;  // uniform: nothing consumes dh_{-1} unless dh0 is asked for
+        __syncthreads();                       // dpre_t of the group in LDS
         // dh_{t-1}[j] (recurrent part) = sum_r dpre_t[r] * W_hh[r][j]
         v2f acc[G / 2];
 #pragma unroll
@@ -377,6 +418,19 @@ lstm_seq_bwd_kernel(const float* __restrict__ gates, const float* __restrict__ c
             for (int g = 0; g < G; ++g) dhr[g] = (g & 1) ? acc[g / 2].y : acc[g / 2].x;
         }
         // the next step's partial writes come after its first barrier, so these reads are ordered
+    }
+    if constexpr (STATE) {
+        if (dh0 && s == 0 && unit) {  // dhr = W_hh^T dpre_0 and dc = dc_0 f_0 now; length 0: dhn / dcn pass through
+#pragma unroll
+            for (int g = 0; g < G; ++g) {
+                if (g >= nb) {
+                    continue;
+                }
+                const int64_t at = (int64_t)(b0 + g) * H + j;
+                dh0[at] = ln[g] ? dhr[g] : (dhn ? dhn[at] : 0.f);
+                dc0[at] = ln[g] ? dc[g] : (dcn ? dcn[at] : 0.f);
+            }
+        }
     }
 }
 
@@ -588,6 +642,27 @@ int vc_lstm_seq_fwd_state(const float* pre, int64_t ldpre, int64_t B, const int3
     return check_launch("vc_lstm_seq_fwd_state");
 }
 
+int vc_lstm_seq_fwd_train_state(const float* pre, int64_t ldpre, int64_t B, const int32_t* row0, const int32_t* len,
+                                int64_t max_len, int64_t hidden, const float* W_hh_t, const float* h0, const float* c0,
+                                const float* keep, uint16_t* h_seq, int64_t ldh, float* h_n, float* c_n, float* gates,
+                                float* c_seq, uint16_t* h_prev, int64_t ldhp, hipStream_t stream) {
+    if (!pre || !W_hh_t || !h_seq || !h_n || !c_n || !gates || !c_seq || !h_prev)
+        return fail(VC_ERR_INVALID_ARG, "vc_lstm_seq_fwd_train_state: null pointer");
+    if (!row0 != !len)
+        return fail(VC_ERR_INVALID_ARG, "vc_lstm_seq_fwd_train_state: row0 and len come together (both null: the dense layout)");
+    if (!h0 != !c0)
+        return fail(VC_ERR_INVALID_ARG, "vc_lstm_seq_fwd_train_state: h0 and c0 come together (both null: the zero state)");
+    if (const char* m = check_hidden(B, max_len, hidden))
+        return fail(VC_ERR_INVALID_ARG, std::string("vc_lstm_seq_fwd_train_state (T = max_len): ") + m);
+    if (ldpre < 4 * hidden || ldh < hidden || ldhp < hidden)
+        return fail(VC_ERR_INVALID_ARG, "vc_lstm_seq_fwd_train_state: row stride below the row length");
+    const SeqLaunch L(B, hidden);
+    L.run(lstm_seq_fwd_kernel<4, true, true, true>, lstm_seq_fwd_kernel<2, true, true, true>, L.lds_fwd(), stream, pre, ldpre,
+          (int)B, (int)max_len, L.H, W_hh_t, row0, len, keep, h_seq, ldh, nullptr, gates, c_seq, h_prev, ldhp, h0, c0, h_n,
+          c_n, nullptr, 0);
+    return check_launch("vc_lstm_seq_fwd_train_state");
+}
+
 int vc_lstm_seq_bwd(const float* gates, const float* c_seq, int64_t B, int64_t T, int64_t hidden, const float* W_hh,
                     const float* dh, int64_t lddh, int last_only, const float* keep, float* dpre, uint16_t* dpre_bf16,
                     int64_t lddb, hipStream_t stream) {
@@ -596,8 +671,26 @@ int vc_lstm_seq_bwd(const float* gates, const float* c_seq, int64_t B, int64_t T
     if (lddh < hidden || lddb < 4 * hidden) return fail(VC_ERR_INVALID_ARG, "vc_lstm_seq_bwd: row stride below the row length");
     const SeqLaunch L(B, hidden);
     L.run(lstm_seq_bwd_kernel<4>, lstm_seq_bwd_kernel<2>, L.lds_bwd(), stream, gates, c_seq, (int)B, (int)T, L.H, W_hh, dh,
-          lddh, last_only, keep, dpre, dpre_bf16, lddb);
+          lddh, last_only, keep, dpre, dpre_bf16, lddb, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
     return check_launch("vc_lstm_seq_bwd");
+}
+
+int vc_lstm_seq_bwd_state(const float* gates, const float* c_seq, const float* c0, int64_t B, const int32_t* row0,
+                          const int32_t* len, int64_t max_len, int64_t hidden, const float* W_hh, const float* dh_seq,
+                          int64_t lddh, const float* keep, const float* dh_n, const float* dc_n, float* dpre,
+                          uint16_t* dpre_bf16, int64_t lddb, float* dh0, float* dc0, hipStream_t stream) {
+    if (!gates || !c_seq || !W_hh || !dpre || !dpre_bf16) return fail(VC_ERR_INVALID_ARG, "vc_lstm_seq_bwd_state: null pointer");
+    if (!row0 != !len)
+        return fail(VC_ERR_INVALID_ARG, "vc_lstm_seq_bwd_state: row0 and len come together (both null: the dense layout)");
+    if (!dh0 != !dc0) return fail(VC_ERR_INVALID_ARG, "vc_lstm_seq_bwd_state: dh0 and dc0 come together (both null: not wanted)");
+    if (const char* m = check_hidden(B, max_len, hidden))
+        return fail(VC_ERR_INVALID_ARG, std::string("vc_lstm_seq_bwd_state (T = max_len): ") + m);
+    if ((dh_seq && lddh < hidden) || lddb < 4 * hidden)
+        return fail(VC_ERR_INVALID_ARG, "vc_lstm_seq_bwd_state: row stride below the row length");
+    const SeqLaunch L(B, hidden);
+    L.run(lstm_seq_bwd_kernel<4, true>, lstm_seq_bwd_kernel<2, true>, L.lds_bwd(), stream, gates, c_seq, (int)B, (int)max_len,
+          L.H, W_hh, dh_seq, lddh, 0, keep, dpre, dpre_bf16, lddb, row0, len, c0, dh_n, dc_n, dh0, dc0);
+    return check_launch("vc_lstm_seq_bwd_state");
 }
 
 int vc_mlp_head_fwd(const float* h, int64_t B, int64_t hidden, const float* W1, const float* b1, int64_t H1,

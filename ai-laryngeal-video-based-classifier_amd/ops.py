@@ -1198,6 +1198,46 @@ def lstm_seq_fwd_ragged(pre: torch.Tensor, lengths, hidden: int, w_hh_t: torch.T
     return h_last
 
 
+def _lstm_state_layout(name: str, B: int, hidden: int, lengths, row0, T):
+    """The row layout of the stateful entry points (lstm_seq_fwd_state, lstm_seq_fwd_train_state, lstm_seq_bwd_state),
+    ragged (lengths, row0) or dense (lengths=None, T), over B state rows: (lengths or None, row0 or None, max_len,
+    rows the dense layout needs, steps per sequence group)."""
+    if lengths is None:
+        _need(T is not None and row0 is None, f"{name}: the dense layout (lengths=None) takes T and no row0")
+        T = int(T)
+        _lstm_shape(B, T, hidden)
+        return None, None, T, B * T, [T] * -(-B // lstm_group(hidden))
+    lengths = tuple(int(n) for n in lengths)
+    _need(T is None, f"{name}: T belongs to the dense layout (lengths=None)")
+    _need(len(lengths) >= 1 and all(n >= 0 for n in lengths), f"{name}: lengths must be a non-empty sequence of ints >= 0")
+    _need(len(lengths) == B, f"{name}: {len(lengths)} lengths for B = {B}: the state holds one row per sequence")
+    max_len = max(1, max(lengths))
+    _lstm_shape(B, max_len, hidden)
+    G = lstm_group(hidden)
+    return lengths, _ragged_row0(name, lengths, row0), max_len, 0, [max(lengths[i:i + G]) for i in range(0, B, G)]
+
+
+def _lstm_state_rows(name: str, what: str, t: torch.Tensor, dtype, min_rows: int, cols: int) -> int:
+    _need(t.dtype == dtype and t.dim() == 2 and t.stride(1) == 1 and t.shape[0] >= min_rows and t.shape[1] >= cols,
+          f"{name}: {what} [rows, >= {cols}] with unit column stride")
+    return t.shape[0]
+
+
+def _lstm_state_vectors(name: str, B: int, hidden: int, h_n, c_n, h0, c0) -> list:
+    """(h0, c0) in and (h_n, c_n) out, as the stateful forwards take them; returns [h0, c0], or [] for the zero state."""
+    _need((h0 is None) == (c0 is None), f"{name}: h0 and c0 come together (both None: the zero state)")
+    state = [t for t in (h0, c0) if t is not None]
+    _dev(c_n, *state)
+    for t in (h_n, c_n, *state):
+        _need(t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (B, hidden),
+              f"{name}: h0, c0, h_n and c_n are f32 contiguous [B, H]")
+    span = B * hidden * 4
+    for a, b, ok in ((h_n, c_n, False), (h_n, c0, False), (c_n, h0, False), (h_n, h0, True), (c_n, c0, True)):
+        if b is not None and abs(_p(a) - _p(b)) < span:  # overlapping storage: only the exact in-place pairs
+            _need(ok and _p(a) == _p(b), f"{name}: h_n may alias h0 and c_n may alias c0 exactly, nothing else")
+    return state
+
+
 def lstm_seq_fwd_state(pre: torch.Tensor, lengths, hidden: int, w_hh_t: torch.Tensor, h_seq: torch.Tensor,
                        h_n: torch.Tensor, c_n: torch.Tensor, h0: torch.Tensor | None = None,
                        c0: torch.Tensor | None = None, h_all: torch.Tensor | None = None, row0=None,
@@ -1212,45 +1252,19 @@ def lstm_seq_fwd_state(pre: torch.Tensor, lengths, hidden: int, w_hh_t: torch.Te
     name = "lstm_seq_fwd_state"
     _need(isinstance(h_n, torch.Tensor) and h_n.dim() == 2, f"{name}: h_n f32 [B, H]")
     B = h_n.shape[0]
-    if lengths is None:
-        _need(T is not None and row0 is None, f"{name}: the dense layout (lengths=None) takes T and no row0")
-        T = int(T)
-        _lstm_shape(B, T, hidden)
-        max_len, min_rows = T, B * T
-    else:
-        lengths = tuple(int(n) for n in lengths)
-        _need(T is None, f"{name}: T belongs to the dense layout (lengths=None)")
-        _need(len(lengths) >= 1 and all(n >= 0 for n in lengths),
-              f"{name}: lengths must be a non-empty sequence of ints >= 0")
-        _need(len(lengths) == B, f"{name}: h_n must hold one row per sequence")
-        max_len, min_rows = max(1, max(lengths)), 0
-        _lstm_shape(B, max_len, hidden)
-        row0 = _ragged_row0(name, lengths, row0)
+    lengths, row0, max_len, min_rows, group_steps = _lstm_state_layout(name, B, hidden, lengths, row0, T)
     _lstm_fwd_operands(name, "rows", min_rows, B, hidden, pre, w_hh_t, h_seq, h_n)
-    _need((h0 is None) == (c0 is None), f"{name}: h0 and c0 come together (both None: the zero state)")
-    state = [t for t in (h0, c0) if t is not None]
-    _dev(c_n, *state)
-    for t in (h_n, c_n, *state):
-        _need(t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (B, hidden),
-              f"{name}: h0, c0, h_n and c_n are f32 contiguous [B, H]")
-    span = B * hidden * 4
-    for a, b, ok in ((h_n, c_n, False), (h_n, c0, False), (c_n, h0, False), (h_n, h0, True), (c_n, c0, True)):
-        if b is not None and abs(_p(a) - _p(b)) < span:  # overlapping storage: only the exact in-place pairs
-            _need(ok and _p(a) == _p(b), f"{name}: h_n may alias h0 and c_n may alias c0 exactly, nothing else")
+    state = _lstm_state_vectors(name, B, hidden, h_n, c_n, h0, c0)
     rows = min(pre.shape[0], h_seq.shape[0])
     if h_all is not None:
         _dev(h_all)
         _need(h_all.dtype == torch.float32 and h_all.dim() == 2 and h_all.shape[0] >= min_rows and
               h_all.shape[1] >= hidden and h_all.stride(1) == 1, f"{name}: h_all f32 [rows, >= H]")
         rows = min(rows, h_all.shape[0])
-    G = lstm_group(hidden)
-    if lengths is None:
-        d_row0 = d_len = None
-        group_steps = [T] * -(-B // G)
-    else:
+    d_row0 = d_len = None
+    if lengths is not None:
         _ragged_inside(name, lengths, row0, rows, "pre / h_seq / h_all")
         d_row0, d_len = _ragged_tables(lengths, row0, pre.device)
-        group_steps = [max(lengths[i:i + G]) for i in range(0, B, G)]
     # W_hh is streamed once per step and group; from the zero state step 0 has no product
     steps = sum(n if state else max(n - 1, 0) for n in group_steps)
     timed("lstm_seq_fwd_state_kernel", "lstm_fwd", 4.0 * hidden * hidden * 4 * steps, "byte", _lib.call,
@@ -1289,6 +1303,102 @@ def lstm_seq_bwd(gates: torch.Tensor, c_seq: torch.Tensor, B: int, T: int, hidde
     timed("lstm_seq_bwd_kernel", "lstm_bwd", 4.0 * hidden * hidden * 4 * T * ngroups, "byte", _lib.call,
           "vc_lstm_seq_bwd", _p(gates), _p(c_seq), B, T, hidden, _p(w_hh), _p(dh), dh.stride(0), int(last_only),
           _p(keep) if keep is not None else None, _p(dpre), _p(dpre_bf16), dpre_bf16.stride(0), _stream(gates))
+    return dpre
+
+
+def lstm_seq_fwd_train_state(pre: torch.Tensor, lengths, hidden: int, w_hh_t: torch.Tensor, h_seq: torch.Tensor,
+                             h_n: torch.Tensor, c_n: torch.Tensor, gates: torch.Tensor, c_seq: torch.Tensor,
+                             h_prev: torch.Tensor, h0: torch.Tensor | None = None, c0: torch.Tensor | None = None,
+                             keep: torch.Tensor | None = None, row0=None, T: int | None = None) -> tuple:
+    """The train variant of lstm_seq_fwd_state (same layout, state and aliasing rules): also writes the saved
+    tensors of lstm_seq_bwd_state, gates f32 [rows, 4H], c_seq f32 [rows, H] (both contiguous) and h_prev bf16
+    [rows, >= H], whose row of a sequence's first step is bf16(h0) (zero without a state); keep f32 [rows, H]
+    (optional, contiguous) scales the stored h_seq only.  Bit-identical to lstm_seq_fwd (train variant) from
+    the zero state at full lengths, to lstm_seq_fwd_state in h_seq / h_n / c_n, and chunked to whole."""
+    name = "lstm_seq_fwd_train_state"
+    _need(isinstance(h_n, torch.Tensor) and h_n.dim() == 2, f"{name}: h_n f32 [B, H]")
+    B = h_n.shape[0]
+    lengths, row0, max_len, min_rows, group_steps = _lstm_state_layout(name, B, hidden, lengths, row0, T)
+    _lstm_fwd_operands(name, "rows", min_rows, B, hidden, pre, w_hh_t, h_seq, h_n)
+    state = _lstm_state_vectors(name, B, hidden, h_n, c_n, h0, c0)
+    _dev(gates, c_seq, h_prev)
+    rows = min(pre.shape[0], h_seq.shape[0])
+    _need(gates.is_contiguous() and c_seq.is_contiguous(), f"{name}: gates and c_seq are contiguous")
+    rows = min(rows, _lstm_state_rows(name, "gates f32", gates, torch.float32, min_rows, 4 * hidden),
+               _lstm_state_rows(name, "c_seq f32", c_seq, torch.float32, min_rows, hidden),
+               _lstm_state_rows(name, "h_prev bf16", h_prev, torch.bfloat16, min_rows, hidden))
+    _need(gates.shape[1] == 4 * hidden and c_seq.shape[1] == hidden, f"{name}: gates f32 [rows, 4H], c_seq f32 [rows, H]")
+    if keep is not None:
+        _dev(keep)
+        _need(keep.is_contiguous() and keep.shape[-1] == hidden, f"{name}: keep f32 contiguous [rows, H]")
+        rows = min(rows, _lstm_state_rows(name, "keep f32", keep, torch.float32, min_rows, hidden))
+    d_row0 = d_len = None
+    if lengths is not None:
+        _ragged_inside(name, lengths, row0, rows, "pre / h_seq / gates / c_seq / h_prev / keep")
+        d_row0, d_len = _ragged_tables(lengths, row0, pre.device)
+    steps = sum(n if state else max(n - 1, 0) for n in group_steps)
+    timed("lstm_seq_fwd_train_state_kernel", "lstm_fwd", 4.0 * hidden * hidden * 4 * steps, "byte", _lib.call,
+          "vc_lstm_seq_fwd_train_state", _p(pre), pre.stride(0), B, _p(d_row0) if d_row0 is not None else None,
+          _p(d_len) if d_len is not None else None, max_len, hidden, _p(w_hh_t), _p(h0) if state else None,
+          _p(c0) if state else None, _p(keep) if keep is not None else None, _p(h_seq), h_seq.stride(0), _p(h_n), _p(c_n),
+          _p(gates), _p(c_seq), _p(h_prev), h_prev.stride(0), _stream(pre))
+    return h_n, c_n
+
+
+def lstm_seq_bwd_state(gates: torch.Tensor, c_seq: torch.Tensor, B: int, lengths, hidden: int, w_hh: torch.Tensor,
+                       dpre: torch.Tensor, dpre_bf16: torch.Tensor, dh_seq: torch.Tensor | None = None,
+                       dh_n: torch.Tensor | None = None, dc_n: torch.Tensor | None = None,
+                       c0: torch.Tensor | None = None, keep: torch.Tensor | None = None,
+                       dh0: torch.Tensor | None = None, dc0: torch.Tensor | None = None, row0=None,
+                       T: int | None = None) -> torch.Tensor:
+    """BPTT of lstm_seq_fwd_train_state from its gates / c_seq, over the same layout (lengths + row0, or
+    lengths=None and T).  Incoming, each optional: dh_seq f32 [rows, >= H] (times keep f32 [rows, H] when
+    given), dh_n and dc_n f32 [B, H] (never masked; they enter at each sequence's last step).  c0 f32 [B, H]
+    is the state the forward started from (None: zeros).  Writes dpre f32 [rows, 4H] and dpre_bf16 for the
+    rows of the sequences only; dh0 / dc0 f32 [B, H] (both or neither) get the gradient of the incoming
+    state, dh_n / dc_n passed through for a sequence of length 0.  dh0 may be dh_n and dc0 may be dc_n."""
+    name = "lstm_seq_bwd_state"
+    _need(isinstance(B, int) and B >= 1, f"{name}: B must be an int >= 1")
+    lengths, row0, max_len, min_rows, group_steps = _lstm_state_layout(name, B, hidden, lengths, row0, T)
+    _dev(gates, c_seq, w_hh, dpre, dpre_bf16)
+    _need(gates.is_contiguous() and c_seq.is_contiguous() and dpre.is_contiguous(),
+          f"{name}: gates, c_seq and dpre are contiguous")
+    rows = min(_lstm_state_rows(name, "gates f32", gates, torch.float32, min_rows, 4 * hidden),
+               _lstm_state_rows(name, "c_seq f32", c_seq, torch.float32, min_rows, hidden),
+               _lstm_state_rows(name, "dpre f32", dpre, torch.float32, min_rows, 4 * hidden),
+               _lstm_state_rows(name, "dpre_bf16 bf16", dpre_bf16, torch.bfloat16, min_rows, 4 * hidden))
+    _need(gates.shape[1] == 4 * hidden and c_seq.shape[1] == hidden and dpre.shape[1] == 4 * hidden,
+          f"{name}: gates and dpre f32 [rows, 4H], c_seq f32 [rows, H]")
+    _need(w_hh.dtype == torch.float32 and w_hh.is_contiguous() and tuple(w_hh.shape) == (4 * hidden, hidden),
+          f"{name}: w_hh f32 contiguous [4H, H]")
+    if dh_seq is not None:
+        _dev(dh_seq)
+        rows = min(rows, _lstm_state_rows(name, "dh_seq f32", dh_seq, torch.float32, min_rows, hidden))
+    if keep is not None:
+        _dev(keep)
+        _need(keep.is_contiguous() and keep.shape[-1] == hidden, f"{name}: keep f32 contiguous [rows, H]")
+        rows = min(rows, _lstm_state_rows(name, "keep f32", keep, torch.float32, min_rows, hidden))
+    _need((dh0 is None) == (dc0 is None), f"{name}: dh0 and dc0 come together (both None: not wanted)")
+    vecs = [t for t in (dh_n, dc_n, c0, dh0, dc0) if t is not None]
+    _dev(*vecs)
+    for t in vecs:
+        _need(t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (B, hidden),
+              f"{name}: c0, dh_n, dc_n, dh0 and dc0 are f32 contiguous [B, H]")
+    span = B * hidden * 4
+    for a, b, ok in ((dh0, dc0, False), (dh0, dc_n, False), (dc0, dh_n, False), (dh0, c0, False), (dc0, c0, False),
+                     (dh0, dh_n, True), (dc0, dc_n, True)):
+        if a is not None and b is not None and abs(_p(a) - _p(b)) < span:
+            _need(ok and _p(a) == _p(b), f"{name}: dh0 may alias dh_n and dc0 may alias dc_n exactly, nothing else")
+    d_row0 = d_len = None
+    if lengths is not None:
+        _ragged_inside(name, lengths, row0, rows, "gates / c_seq / dpre / dpre_bf16 / dh_seq / keep")
+        d_row0, d_len = _ragged_tables(lengths, row0, gates.device)
+    o = lambda t: _p(t) if t is not None else None  # noqa: E731
+    steps = sum(n if dh0 is not None else max(n - 1, 0) for n in group_steps)  # W_hh is streamed once per product
+    timed("lstm_seq_bwd_state_kernel", "lstm_bwd", 4.0 * hidden * hidden * 4 * steps, "byte", _lib.call,
+          "vc_lstm_seq_bwd_state", _p(gates), _p(c_seq), o(c0), B, o(d_row0), o(d_len), max_len, hidden, _p(w_hh), o(dh_seq),
+          dh_seq.stride(0) if dh_seq is not None else 0, o(keep), o(dh_n), o(dc_n), _p(dpre), _p(dpre_bf16),
+          dpre_bf16.stride(0), o(dh0), o(dc0), _stream(gates))
     return dpre
 
 

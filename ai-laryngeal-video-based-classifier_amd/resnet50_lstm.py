@@ -23,6 +23,11 @@ Inference beyond the reference: `forward_ragged` batches videos of different len
 `init_state` / `forward_stream` carry nn.LSTM's (h, c) from call to call (vc_lstm_seq_fwd_state), so a
 recording of any length runs in chunks at bounded memory, with a logit after every frame.
 
+Training beyond the reference: `forward_train_stream` is the train step on such chunks, over whole videos
+of different lengths with the state carried (autograd_ops.lstm_layer_state on vc_lstm_seq_fwd_train_state /
+vc_lstm_seq_bwd_state): the state it returns stays in the autograd graph (full BPTT across the chunks)
+until the caller takes `LstmState.detach()` (truncated BPTT).
+
 State dict keys are the reference's (resnet50.<child>..., lstm.*, classifier.*).
 """
 from __future__ import annotations
@@ -43,9 +48,13 @@ HEAD_DIM = 64  # classifier.0: Linear(hidden, 64)
 
 
 class LstmState(NamedTuple):
-    """nn.LSTM's (h_n, c_n): f32 [num_layers, B, hidden] each (init_state, forward_stream)."""
+    """nn.LSTM's (h_n, c_n): f32 [num_layers, B, hidden] each (init_state, forward_stream, forward_train_stream)."""
     h: torch.Tensor
     c: torch.Tensor
+
+    def detach(self) -> "LstmState":
+        """A copy cut off from the autograd graph: what truncated BPTT carries from chunk to chunk."""
+        return LstmState(self.h.detach().clone(), self.c.detach().clone())
 
 
 class VideoResNet50LSTM(torch.nn.Module):
@@ -344,6 +353,17 @@ class VideoResNet50LSTM(torch.nn.Module):
         Eval mode only, as forward_ragged."""
         if self.training:
             raise RuntimeError("forward_stream is the inference path: call model.eval() first")
+        x, lengths, B = self._stream_args(video, lengths, state)
+        with torch.no_grad():
+            new = LstmState(torch.empty(self.layers, B, self.hidden, dtype=torch.float32, device=x.device),
+                            torch.empty(self.layers, B, self.hidden, dtype=torch.float32, device=x.device))
+            logits, frames = self._infer(x, lengths, (state, new, frame_logits))
+            logits = logits.clone()  # the workspace buffer is reused by the next call
+        return (logits, new, frames) if frame_logits else (logits, new)
+
+    def _stream_args(self, video, lengths, state):
+        """The layout forward_stream and forward_train_stream take, checked on the host: (f32 contiguous video,
+        lengths as a tuple of ints, B)."""
         if not isinstance(video, torch.Tensor):
             raise TypeError("video must be a tensor")
         lengths = tuple(int(n) for n in lengths)
@@ -360,13 +380,52 @@ class VideoResNet50LSTM(torch.nn.Module):
                         tuple(t.shape) != (self.layers, B, self.hidden) or not t.is_contiguous():
                     raise ValueError(f"state.h / state.c must be f32 contiguous [{self.layers}, {B}, {self.hidden}] on "
                                      f"{video.device} (init_state({B}))")
-        x = video.contiguous().float() if video.dtype != torch.float32 else video.contiguous()
-        with torch.no_grad():
-            new = LstmState(torch.empty(self.layers, B, self.hidden, dtype=torch.float32, device=x.device),
-                            torch.empty(self.layers, B, self.hidden, dtype=torch.float32, device=x.device))
-            logits, frames = self._infer(x, lengths, (state, new, frame_logits))
-            logits = logits.clone()  # the workspace buffer is reused by the next call
-        return (logits, new, frames) if frame_logits else (logits, new)
+        return (video.contiguous().float() if video.dtype != torch.float32 else video.contiguous()), lengths, B
+
+    def forward_train_stream(self, video: torch.Tensor, lengths, state: LstmState | None = None):
+        """The train step on the next frames of len(lengths) whole videos, with the LSTM state carried: the
+        layout, `lengths` and `state` are forward_stream's (`video` f32 [1, 3, N, H, W], N == sum(lengths) >= 1,
+        a length may be 0).  Returns (logits f32 [B, 1], new_state): the head on the top layer's h_n, and an
+        LstmState whose h and c are ATTACHED to the autograd graph.  Feed it to the next call as it is and
+        one backward() from the last logits is exact BPTT over the whole videos (every chunk's saved tensors
+        stay alive until then); feed `new_state.detach()` and the gradient stops at the chunk boundary
+        (truncated BPTT, memory bounded by the chunk).
+        Every call draws fresh dropout masks from torch's RNG, the inter-layer one over the N rows and the
+        head's [B, 64], recorded in `last_keep`.  Each layer is autograd_ops.lstm_layer_state (one projection
+        GEMM, vc_lstm_seq_fwd_train_state, backward vc_lstm_seq_bwd_state).
+        The backbone's BatchNorm follows `freeze_backbone_bn` as in `forward`; with batch statistics (False) the
+        N frames of a call share their statistics across the videos and the running statistics move once per
+        call, so chunked training wants `freeze_backbone_bn = True`.
+        Training mode only; forward_stream is the eval-mode path."""
+        if not self.training:
+            raise RuntimeError("forward_train_stream is the train step: call model.train() first "
+                               "(forward_stream is the eval-mode path)")
+        x, lengths, B = self._stream_args(video, lengths, state)
+        N = x.shape[2]
+        dev = x.device
+        x = self.features(x, train_bn=not self.freeze_backbone_bn)[:N]
+        pk = self._pack(dev)
+        p = self.dropout
+        keeps, hs, cs = [], [], []
+        for l in range(self.layers):
+            keep = None
+            if p > 0.0 and l < self.layers - 1:  # nn.LSTM: dropout on the outputs of every layer but the last
+                keep = torch.ones(N, self.hidden, device=dev).bernoulli_(1.0 - p).mul_(1.0 / (1.0 - p))
+            keeps.append(keep)
+            x, h_n, c_n = A.lstm_layer_state(x, self.P(f"lstm.weight_ih_l{l}"), self.P(f"lstm.weight_hh_l{l}"),
+                                             self.P(f"lstm.bias_ih_l{l}"), self.P(f"lstm.bias_hh_l{l}"), list(lengths),
+                                             h0=None if state is None else state.h[l],
+                                             c0=None if state is None else state.c[l], keep=keep, need_dx=l > 0,
+                                             packed=pk["layers"][l])
+            hs.append(h_n)
+            cs.append(c_n)
+        hkeep = None
+        if p > 0.0:
+            hkeep = torch.ones(B, HEAD_DIM, device=dev).bernoulli_(1.0 - p).mul_(1.0 / (1.0 - p))
+        self.last_keep = {"lstm": keeps, "head": hkeep}
+        logits = A.mlp_head(hs[-1], self.P("classifier.0.weight"), self.P("classifier.0.bias"),
+                            self.P("classifier.3.weight"), self.P("classifier.3.bias"), hkeep)
+        return logits, LstmState(torch.stack(hs), torch.stack(cs))
 
     def forward_ragged(self, video: torch.Tensor, lengths) -> torch.Tensor:
         """Batched inference over videos of different lengths: `video` f32 [1, 3, N, H, W] holds the frames of

@@ -763,12 +763,33 @@ int vc_lstm_seq_fwd_ragged(const float* pre, int64_t ldpre, int64_t B, const int
  * to them, an explicit all-zero state is bit-identical to the NULL state (finite weights), and a sequence
  * run in chunks with the state carried is bit-identical (h_seq, final h and c) to the same sequence
  * run whole.  Deterministic, no atomics.  hidden % 4 == 0, hidden <= 1024; B, max_len >= 1.
- * Inference only: vc_lstm_seq_bwd takes no initial state.
+ * The inference variant: it saves nothing for a backward; vc_lstm_seq_fwd_train_state is the train variant.
  */
 int vc_lstm_seq_fwd_state(const float* pre, int64_t ldpre, int64_t B, const int32_t* row0, const int32_t* len,
                           int64_t max_len, int64_t hidden, const float* W_hh_t, const float* h0, const float* c0,
                           uint16_t* h_seq, int64_t ldh, float* h_all, int64_t ldha, float* h_n, float* c_n,
                           hipStream_t stream);
+
+/*
+ * The train variant of the stateful recurrence: training on whole videos of different lengths in chunks,
+ * with the state carried from chunk to chunk.  Layout (row0, len, max_len), h0 / c0 and h_n / c_n are
+ * those of vc_lstm_seq_fwd_state (h_n, c_n unmasked; a sequence of length 0 passes its state through).
+ *   keep    optional f32 [rows][hidden], indexed by the same row as pre: scales the stored h_seq only;
+ *   gates   f32 [rows][4*hidden] post-activation, c_seq f32 [rows][hidden], h_prev bf16 [rows][hidden]
+ *           (stride ldhp), all required: what vc_lstm_seq_bwd_state and the W_hh gradient need.
+ *           h_prev of a sequence's first step is bf16(h0[b]), zero without a state: with it
+ *           dW_hh = dpre^T h_prev covers the carried state too.
+ * A sequence past its end reads no row and writes no row of any output.  It is one more instantiation of
+ * the step loop of the other three entry points: from a NULL state with full lengths every output is
+ * bit-identical to vc_lstm_seq_fwd (train variant); h_seq, h_n and c_n are bit-identical to
+ * vc_lstm_seq_fwd_state on the same input; and a sequence run in chunks with the state carried is
+ * bit-identical in gates, c_seq and h_prev to the same sequence run whole.  Deterministic, no atomics.
+ * hidden % 4 == 0, hidden <= 1024; B, max_len >= 1.
+ */
+int vc_lstm_seq_fwd_train_state(const float* pre, int64_t ldpre, int64_t B, const int32_t* row0, const int32_t* len,
+                                int64_t max_len, int64_t hidden, const float* W_hh_t, const float* h0, const float* c0,
+                                const float* keep, uint16_t* h_seq, int64_t ldh, float* h_n, float* c_n, float* gates,
+                                float* c_seq, uint16_t* h_prev, int64_t ldhp, hipStream_t stream);
 
 /*
  * The backward of vc_lstm_seq_fwd (train variant) through time, t = T-1 .. 0 in one launch, from the saved gates and c_seq.
@@ -783,6 +804,31 @@ int vc_lstm_seq_fwd_state(const float* pre, int64_t ldpre, int64_t B, const int3
 int vc_lstm_seq_bwd(const float* gates, const float* c_seq, int64_t B, int64_t T, int64_t hidden, const float* W_hh,
                     const float* dh, int64_t lddh, int last_only, const float* keep, float* dpre, uint16_t* dpre_bf16,
                     int64_t lddb, hipStream_t stream);
+
+/*
+ * The backward of vc_lstm_seq_fwd_train_state: BPTT over each sequence from its own last step back to step 0,
+ * with the gradients of the outgoing state coming in and those of the incoming state going out, so that
+ * chunks of a long sequence chain backwards (the later chunk's dh0 / dc0 are the earlier chunk's dh_n / dc_n).
+ *   gates, c_seq, row0, len, max_len   as the forward left them (row0 and len both NULL: the dense layout);
+ *   c0      f32 [B][hidden], nullable (zeros): the c_{-1} of the forget-gate gradient of step 0;
+ *   dh_seq  f32 rows (stride lddh), nullable: dL/d(h_seq), multiplied by keep[row] when keep != NULL;
+ *   dh_n, dc_n  f32 [B][hidden], each nullable, never masked: dL/d(h_n), dL/d(c_n).  They enter at the
+ *           sequence's last valid step: dh_n adds to that step's dh, dc_n to its dc.
+ * Writes dpre f32 [rows][4*hidden] and dpre_bf16 (stride lddb) for the rows of the sequences and no other row
+ * (in the dense layout every sequence is max_len long, so every row is written).  Optional, both or neither:
+ *   dh0     f32 [B][hidden] = W_hh^T dpre_0, the product vc_lstm_seq_bwd skips at t = 0;
+ *   dc0     f32 [B][hidden] = dc_0 * f_0.
+ * A sequence of length 0 passes dh_n / dc_n through to dh0 / dc0 (zeros where those are NULL).  dh0 may
+ * alias dh_n and dc0 may alias dc_n.  A workgroup loops from the largest length of its group; a sequence
+ * that has not started contributes zero rows.  Same grouping, partial-sum order and determinism as
+ * vc_lstm_seq_bwd, no atomics, all arithmetic fp32: with the dense layout, c0 = dh_n = dc_n = NULL, dpre is
+ * bit-identical to vc_lstm_seq_bwd (last_only = 1 corresponds to dh_seq = NULL with dh_n given), and the
+ * backward over two chunks chained through dh0 / dc0 is bit-identical to the backward over the whole sequence.
+ */
+int vc_lstm_seq_bwd_state(const float* gates, const float* c_seq, const float* c0, int64_t B, const int32_t* row0,
+                          const int32_t* len, int64_t max_len, int64_t hidden, const float* W_hh, const float* dh_seq,
+                          int64_t lddh, const float* keep, const float* dh_n, const float* dc_n, float* dpre,
+                          uint16_t* dpre_bf16, int64_t lddb, float* dh0, float* dc0, hipStream_t stream);
 
 /*
  * The classifier Linear(hidden, H1) -> ReLU -> Dropout -> Linear(H1, num_labels) on f32 h [B][hidden]:

@@ -5,7 +5,8 @@ layer 0 with Din 2048, layer 1 with Din 256).
 
 Device events after warm-up, the median of `--reps` (>= 50) repetitions of each: the forward
 (vc_lstm_seq_fwd of libvclip.so), its train variant, the backward kernel (vc_lstm_seq_bwd, full and
-last-step-only) and, unless --no-step, the whole train step (forward, BCE-with-logits loss, backward,
+last-step-only), the stateful train pair (vc_lstm_seq_fwd_train_state / vc_lstm_seq_bwd_state, dense rows
+from the zero state, dh0 / dc0 written) and, unless --no-step, the whole train step (forward, BCE-with-logits loss, backward,
 AdamW) at B = 4, T = 32, 224 x 224.  A report without a bar: compare two builds by running it on each.
 """
 from __future__ import annotations
@@ -80,9 +81,20 @@ def main() -> int:
                  bwd_full_us=_median(lambda: ops.lstm_seq_bwd(gates, cseq, B, T, H, pk["w_hh"], dh, dpre, dpb), reps),
                  bwd_last_only_us=_median(lambda: ops.lstm_seq_bwd(gates, cseq, B, T, H, pk["w_hh"], dhl, dpre, dpb,
                                                                     last_only=True), reps))
+        # the stateful train pair on the same rows from the zero state (dense layout), dh0 / dc0 asked for:
+        # one W_hh product more than the pair above in the backward
+        hn, cn, dh0, dc0 = z(B, H), z(B, H), z(B, H), z(B, H)
+        r.update(fwd_train_state_us=_median(lambda: ops.lstm_seq_fwd_train_state(
+                     pre, None, H, pk["w_hh_t"], hseq, hn, cn, gates, cseq, hprev, T=T), reps),
+                 bwd_state_full_us=_median(lambda: ops.lstm_seq_bwd_state(
+                     gates, cseq, B, None, H, pk["w_hh"], dpre, dpb, dh_seq=dh, dh0=dh0, dc0=dc0, T=T), reps),
+                 bwd_state_last_only_us=_median(lambda: ops.lstm_seq_bwd_state(
+                     gates, cseq, B, None, H, pk["w_hh"], dpre, dpb, dh_n=dhl, dh0=dh0, dc0=dc0, T=T), reps))
         res["layers"][name] = r
         print(f"{name} (Din {din}): fwd {r['fwd_us']:.1f} us, train fwd {r['fwd_train_us']:.1f} us, "
-              f"bwd {r['bwd_full_us']:.1f} us, bwd last-only {r['bwd_last_only_us']:.1f} us", flush=True)
+              f"bwd {r['bwd_full_us']:.1f} us, bwd last-only {r['bwd_last_only_us']:.1f} us; stateful train fwd "
+              f"{r['fwd_train_state_us']:.1f} us, bwd {r['bwd_state_full_us']:.1f} us, bwd last-only "
+              f"{r['bwd_state_last_only_us']:.1f} us", flush=True)
 
     if not a.no_step:
         import torch.nn.functional as F
