@@ -150,18 +150,21 @@ class Family:
         self.name, self.prefix, self.model_dir = name, prefix, model_dir
         self.batch_size, self.epochs, self.lr, self.wd, self.optimizer = batch_size, epochs, lr, wd, optimizer
 
-    def load_clip(self, src, sampler, path, num_frames):
+    def load_clip(self, src, sampler, path, num_frames, want_indices=False):
         """Decoded uint8 frames the transform consumes: the sampled frames (ViViT/TimeSformer,
         resized to 224 as dataset.py:271-277), or every frame of the sampled span (Swin/ResNet3D
-        `get_clip(idx0/fps, (idxN+1)/fps)`, then UniformTemporalSubsample on the GPU)."""
+        `get_clip(idx0/fps, (idxN+1)/fps)`, then UniformTemporalSubsample on the GPU).
+        want_indices (ViViT/TimeSformer): also the source-frame index of each returned frame."""
         idx = sampler.get_sampling_indices(str(path), src.total_frames)
         if isinstance(idx, tuple):
             idx = idx[0]
         if self.name in ("vivit", "timesformer"):
             fr = src.read(idx)  # resized to 224x224 on the GPU (to_model_input), as dataset.py:271-277
+            used = [min(int(i), src.total_frames - 1) for i in idx][:len(fr)]  # read() clamps to the last frame
             if len(fr) < num_frames:  # pad by repeating the last frame (dataset.py:256-265)
+                used += used[-1:] * (num_frames - len(fr))
                 fr = np.concatenate([fr, np.repeat(fr[-1:], num_frames - len(fr), 0)])
-            return fr[:num_frames]
+            return (fr[:num_frames], used[:num_frames]) if want_indices else fr[:num_frames]
         lo, hi = int(min(idx)), int(max(idx))
         return src.read(list(range(lo, hi + 1)))
 
@@ -208,6 +211,13 @@ FAMILIES = {
 }
 
 
+VIVIT_SALIENCY_HELP = (
+    "absent (default): the label only, as the reference.  rollout: attention rollout of the CLS token over every "
+    "layer (VivitForVideoClassification.explain); cls_attention: the last layer's head-mean CLS attention.  Writes "
+    "<video>_saliency.npy (f32 [T/kt, H/kh, W/kw], sums to 1) beside the result JSON, which gains a \"saliency\" "
+    "object with each tubelet's importance and the source-frame indices it covers.")
+
+
 def build_parser(fam: Family, inference: bool):
     if fam.name == "lstm":
         return build_parser_lstm(inference)
@@ -226,6 +236,10 @@ def build_parser(fam: Family, inference: bool):
             p.add_argument("--save_viz", action="store_true")
         else:
             p.add_argument("--visualize", action="store_true")
+        if fam.name == "vivit":
+            # not in the reference, whose HF model can return its attentions: which tubelets produced the label
+            p.add_argument("--saliency", type=str, default=None, choices=["rollout", "cls_attention"],
+                           help=VIVIT_SALIENCY_HELP)
         return p
     required = fam.name in ("swin", "resnet3d")
     p.add_argument("--data_dir", type=str, required=True)
@@ -489,7 +503,10 @@ def run_inference(fam_name, argv=None):
     else:
         sampler = sampling.Resnet3dInferenceSampler(args.num_frames, args.sampling_method, logger,
                                                     fps_of=lambda p: src.fps)
-    frames = torch.from_numpy(fam.load_clip(src, sampler, args.video_path, args.num_frames)).to(device)
+    saliency = getattr(args, "saliency", None)
+    clip = fam.load_clip(src, sampler, args.video_path, args.num_frames, want_indices=bool(saliency))
+    clip, frame_idx = clip if saliency else (clip, None)
+    frames = torch.from_numpy(clip).to(device)
     # the Swin / ResNet3D inference scripts divide by 255 before Normalize (resnet50-3d-video/inference.py:382-394)
     x = fam.to_model_input(frames.unsqueeze(0), args.num_frames, div255=True)
     t0 = time.perf_counter()
@@ -507,6 +524,17 @@ def run_inference(fam_name, argv=None):
            "confidence": conf, "class_mapping": {str(k): v for k, v in id2label.items()}}
     out = exp.get_experiment_dir() / "inference_results"
     out.mkdir(parents=True, exist_ok=True)
+    if saliency:
+        # the label above is the ordinary forward's, the same with and without the flag; the map is explain's
+        ex = model.explain(x, method=saliency)
+        sal = ex.saliency[0].numpy()
+        kt = model.config.tubelet_size[0]
+        npy = f"{Path(args.video_path).stem}_saliency.npy"
+        np.save(out / npy, sal)
+        res["saliency"] = {"method": saliency, "file": npy, "shape": list(sal.shape),
+                           "temporal_importance": [float(v) for v in ex.temporal[0]],
+                           "tubelet_frame_indices": [frame_idx[i:i + kt] for i in range(0, len(frame_idx), kt)]}
+        logger.info(f"Saliency ({saliency}): {out / npy}, most important tubelet {int(ex.temporal[0].argmax())}")
     with open(out / f"{Path(args.video_path).stem}_result.json", "w") as f:
         json.dump(res, f, indent=4)
     return res

@@ -805,6 +805,30 @@ def attention_fwd_lse(qkv: torch.Tensor, B: int, S: int, H: int, out: torch.Tens
     return out
 
 
+def attention_rollout_work(B: int, S: int, H: int, device) -> torch.Tensor:
+    """the f32 per-head partials buffer of attention_rollout_step: one float per (clip, head, token)"""
+    return torch.zeros(B * H * S, dtype=torch.float32, device=device)
+
+
+def attention_rollout_step(qkv: torch.Tensor, lse: torch.Tensor, r_in: torch.Tensor, B: int, S: int, H: int,
+                           alpha: float, work: torch.Tensor, r_out: torch.Tensor) -> torch.Tensor:
+    """One attention-rollout step of the CLS row (vc_attention_rollout_step): r_out = alpha * mean_h(P_h^T r_in)
+    + (1 - alpha) * r_in with P_h recomputed from qkv bf16 [>= B*S, >= 3*H*64] (q pre-scaled) and the lse f32
+    [B*H*S] of attention_fwd_lse.  r_in / r_out f32 [B, S]; work from attention_rollout_work."""
+    _dev(qkv, lse, r_in, work, r_out)
+    _need(lse.dtype == torch.float32 and lse.is_contiguous() and lse.numel() >= B * H * S, "lse: f32 [B*H*S]")
+    _need(qkv.dtype == torch.bfloat16 and qkv.dim() == 2 and qkv.stride(1) == 1, "attention_rollout_step: qkv bf16 rows")
+    _need(qkv.shape[1] >= 3 * H * 64 and qkv.shape[0] >= B * S, "attention_rollout_step: qkv rows / columns")
+    for t, nm in ((r_in, "r_in"), (r_out, "r_out")):
+        _need(t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (B, S),
+              f"attention_rollout_step: {nm} f32 [B, S]")
+    _need(work.dtype == torch.float32 and work.is_contiguous() and work.numel() >= B * H * S,
+          "attention_rollout_step work: contiguous f32 [B*H*S]")
+    _lib.call("vc_attention_rollout_step", _p(qkv), qkv.stride(0), _p(lse), _p(r_in), B, S, H, 64, float(alpha),
+              _p(work), work.numel(), _p(r_out), _stream(qkv))
+    return r_out
+
+
 def attention_bwd(qkv: torch.Tensor, out: torch.Tensor, dout: torch.Tensor, lse: torch.Tensor, delta: torch.Tensor,
                   B: int, S: int, H: int, dqkv: torch.Tensor, stream2: torch.cuda.Stream | None = None) -> torch.Tensor:
     """dqkv (q part = dL/dq' of the stored pre-scaled q', then dk, dv) of the joint attention.

@@ -75,6 +75,16 @@ class VivitConfig:
         return f"VivitConfig({json.dumps(self.to_dict())})"
 
 
+class Explanation:
+    """What VivitForVideoClassification.explain returns: `logits` f32 [B, labels] on the device;
+    `token_relevance` f32 [B, S] (column 0 is CLS), `saliency` f32 [B, T/kt, H/kh, W/kw] (the patch tokens'
+    relevance divided by its per-clip sum) and `temporal` f32 [B, T/kt] (saliency summed over space) on the host."""
+
+    def __init__(self, logits, token_relevance, saliency, temporal, method):
+        self.logits, self.token_relevance, self.saliency, self.temporal = logits, token_relevance, saliency, temporal
+        self.method = method
+
+
 class ClassifierOutput:
     """Mimics the `.logits` / `.loss` access of transformers' ImageClassifierOutput."""
 
@@ -124,6 +134,7 @@ class VivitForVideoClassification(torch.nn.Module):
         self._packed = None
         self._ws = {}
         self._ws_used = []
+        self._explain_ws = {}  # explain()'s own buffers per (B, device): not in _ws, which captured graphs hold on to
         self._streams = None
         self.concurrent_streams = None  # None / 1: one stream; n > 1: batch split over n HIP streams
         # HIP stream priority per part (lower is higher) of the eager forward's part streams, an A/B hook;
@@ -198,6 +209,7 @@ class VivitForVideoClassification(torch.nn.Module):
         self._flat = self._gflat = self._gscratch = self._engine = None
         self._packed = None
         self._ws = {}
+        self._explain_ws = {}
         self._streams = None
         self._graphs.clear()
         return out
@@ -494,9 +506,12 @@ class VivitForVideoClassification(torch.nn.Module):
         go(self._streams)
         return logits
 
-    def _forward_part(self, pix: torch.Tensor, part: int, out=None, cls_only: bool = False) -> torch.Tensor:
+    def _forward_part(self, pix: torch.Tensor, part: int, out=None, cls_only: bool = False, keep=None) -> torch.Tensor:
         """One part's forward.  cls_only = False: every layer over every token row (X ends as the full last
-        hidden state); True: the last layer past its q|k|v GEMM for the CLS rows only, where it can."""
+        hidden state); True: the last layer past its q|k|v GEMM for the CLS rows only, where it can.
+        keep (explain only, bf16, cls_only False): {"QKV": [L, Mpad, 3D], "LSE": [L, B*H*S]} -- layer i's q|k|v
+        goes to keep["QKV"][i] instead of the shared buffer and its attention is ops.attention_fwd_lse, which
+        stores the base-2 log-sum-exp in keep["LSE"][i]."""
         c = self.config
         B = pix.shape[0]
         pk = self._pack(pix.device)
@@ -575,6 +590,8 @@ class VivitForVideoClassification(torch.nn.Module):
                 and ops.skinny_gemm_takes(D) and ops.skinny_gemm_takes(I)):
             n_full -= 1
         for li, L in enumerate(pk["layers"]):
+            if keep is not None:
+                QKV = keep["QKV"][li]
             sp = L.get("split", {})  # the split-operand fp16 GEMMs (precise_layers / precise_ops): A wraps against [W_hi | W_lo]
             run("layernorm", tm, "layernorm_kernel", "layernorm", ln_bytes, "byte", ops.layernorm, X, L["ln1_g"],
                 L["ln1_b"], eps, Y, m=m_ln)
@@ -602,8 +619,12 @@ class VivitForVideoClassification(torch.nn.Module):
                 run("cls_fc2", tm, "skinny_gemm_kernel", "cls_fc2", D * I * es, "byte", ops.skinny_gemm, Hc, L["w_2"],
                     L["b_2"], "bias_resid_f32", Xc)
                 continue
-            run("attention", tm, "attn_fwd_d64_kernel", "attention", attn_flop, "flop", ops.attention, QKV, B, S, Hn,
-                scale, O, q_prescaled=True)
+            if keep is not None:
+                run("attention", tm, "attn_fwd_d64_kernel", "attention", attn_flop, "flop", ops.attention_fwd_lse, QKV,
+                    B, S, Hn, O, keep["LSE"][li], scale=scale, q_prescaled=True)
+            else:
+                run("attention", tm, "attn_fwd_d64_kernel", "attention", attn_flop, "flop", ops.attention, QKV, B, S, Hn,
+                    scale, O, q_prescaled=True)
             if "w_o" in sp:
                 run("o_proj", ops.gemm_wrap, O, D, sp["w_o"], L["b_o"], "bias_resid_f32", X, flop=2.0 * M * D * D,
                     op="o_proj")
@@ -624,6 +645,80 @@ class VivitForVideoClassification(torch.nn.Module):
                     flop=2.0 * M * D * I, op="fc2")
         return ops.cls_head(X, B, S, pk["lnf_g"], pk["lnf_b"], eps, pk["w_cls"], pk["b_cls"],
                             out=ws["logits"] if out is None else out)
+
+
+    # ---- explain ------------------------------------------------------------------
+    EXPLAIN_METHODS = ("rollout", "cls_attention")
+
+    def _explain_buffers(self, B, device):
+        key = (B, str(device))
+        if key not in self._explain_ws:
+            if len(self._explain_ws) >= 2:
+                self._explain_ws = {}
+            c = self.config
+            _, S, Mpad, _ = self.geometry(B)
+            Hn, nl = c.num_attention_heads, c.num_hidden_layers
+            seed = torch.zeros(B, S, dtype=torch.float32)
+            seed[:, 0] = 1.0  # e_CLS, made on the host: one copy, no device arithmetic
+            f = lambda *s: torch.zeros(s, dtype=torch.float32, device=device)  # noqa: E731
+            self._explain_ws[key] = dict(QKV=torch.zeros(nl, Mpad, 3 * c.hidden_size, dtype=torch.bfloat16, device=device),
+                                         LSE=f(nl, B * Hn * S), seed=seed.to(device), r=(f(B, S), f(B, S)),
+                                         work=ops.attention_rollout_work(B, S, Hn, device))
+        return self._explain_ws[key]
+
+    @torch.no_grad()
+    def explain(self, pixel_values: torch.Tensor, method: str = "rollout", residual: float = 0.5) -> Explanation:
+        """The logits and which tokens produced them: attention rollout (Abnar & Zuidema 2020) of the CLS row.
+
+        method "rollout": r = e_CLS, then for layers L .. 1  r <- residual * mean_h(A_h)^T r + (1 - residual) * r,
+        i.e. the CLS row of prod_l (residual * A_l + (1 - residual) * I); "cls_attention": the head-mean CLS
+        attention row of the last layer (one step, no residual mix).  Every step is ops.attention_rollout_step,
+        which recomputes the probabilities from the layer's q|k|v and log-sum-exp: no S x S matrix exists.
+
+        Runs the ordinary full eager forward (every layer over every token, no graph replay, no stream split)
+        with the lse-storing attention kernel and keeps every layer's q|k|v [L, Mpad, 3D] bf16 and lse
+        [L, B*H*S] f32 in buffers of its own, cached per (B, device): about 173 MB per clip at ViViT-B/16x2
+        (184 MB at B = 1 with the row padding).  The forward's workspaces, graphs and logits are untouched.
+        The [B, S] result is copied to the host once; normalisation and the spatial sum happen there.
+        Refuses (no fallback): training mode, CPU tensors, compute_dtype fp16 (the lse forward is bf16-only),
+        precise_layers > 0, head_dim != 64."""
+        c = self.config
+        if method not in self.EXPLAIN_METHODS:
+            raise ValueError(f"explain: method must be one of {self.EXPLAIN_METHODS}, not {method!r}")
+        if not 0.0 < float(residual) <= 1.0:
+            raise ValueError(f"explain: residual must be in (0, 1], not {residual}")
+        if self.training:
+            raise RuntimeError("explain: inference only; call model.eval() first")
+        if pixel_values is None or pixel_values.device.type != "cuda":
+            raise RuntimeError("explain runs on the GPU only: move pixel_values to cuda")
+        if self.compute_dtype != torch.bfloat16:
+            raise RuntimeError("explain: compute_dtype must be torch.bfloat16 (the lse-storing attention forward is bf16-only)")
+        if self.precise_layers > 0:
+            raise RuntimeError("explain: precise_layers > 0 (split-operand fp16 layers) is not supported")
+        if c.hidden_size // c.num_attention_heads != 64:
+            raise RuntimeError("explain: head_dim must be 64")
+        pix = pixel_values.contiguous()
+        if pix.dtype != torch.float32:
+            pix = pix.float()
+        B, T, C, H, W = pix.shape
+        if T != c.num_frames or H != c.image_size or W != c.image_size or C != c.num_channels:
+            raise ValueError(f"pixel_values {tuple(pix.shape)} do not match config "
+                             f"(T={c.num_frames}, C={c.num_channels}, {c.image_size}^2)")
+        _, S, _, _ = self.geometry(B)
+        Hn, nl = c.num_attention_heads, c.num_hidden_layers
+        buf = self._explain_buffers(B, pix.device)
+        logits = self._forward_part(pix, 0, cls_only=False, keep=buf).clone()
+        steps = [(li, float(residual)) for li in reversed(range(nl))] if method == "rollout" else [(nl - 1, 1.0)]
+        r_in = buf["seed"]
+        for k, (li, alpha) in enumerate(steps):
+            r_out = buf["r"][k & 1]
+            ops.attention_rollout_step(buf["QKV"][li], buf["LSE"][li], r_in, B, S, Hn, alpha, buf["work"], r_out)
+            r_in = r_out
+        rel = r_in.cpu()  # the one copy; the rest is host bookkeeping on [B, S]
+        kt, kh, kw = c.tubelet_size
+        patch = rel[:, 1:].double()
+        sal = (patch / patch.sum(dim=1, keepdim=True)).float().reshape(B, T // kt, H // kh, W // kw)
+        return Explanation(logits, rel, sal, sal.sum(dim=(2, 3)), method)
 
 
 def create_model(model_name="google/vivit-b-16x2-kinetics400", num_classes=2, class_labels=None, num_frames=32,

@@ -556,6 +556,25 @@ int vc_attention_fwd_lse(const uint16_t* qkv, int64_t ld, int64_t B, int64_t S, 
                          float scale, int q_prescaled, uint16_t* out, int64_t ldo, float* lse, hipStream_t stream);
 
 /*
+ * One step of attention rollout for the CLS row (csrc/attention_rollout.hip; Abnar & Zuidema 2020,
+ * "Quantifying Attention Flow in Transformers").  No reference counterpart: the reference's HF
+ * models return materialised attentions on request, which a flash kernel never has.  With P_h the
+ * attention probabilities of head h, recomputed as exp2(q'_i . k_j - lse[(b*H + h)*S + i]) from
+ * the q'|k|v rows and the lse of vc_attention_fwd_lse (bf16, head_dim 64):
+ *     u[b][j]     = (1/H) sum_h sum_i r_in[b][i] * P_h[i][j]
+ *     r_out[b][j] = alpha * u[b][j] + (1 - alpha) * r_in[b][j]          (r_in, r_out f32 [B, S])
+ * alpha = 0.5 is the rollout of 0.5 A + 0.5 I; alpha = 1 with r_in = e_CLS is the head-mean CLS
+ * attention row.  The q'.k products are bf16 MFMA with fp32 accumulation, P and the sums stay fp32.
+ * work: caller scratch, work_elems >= B*H*S floats (per-head partials, summed in head order by a
+ * second launch); nothing is allocated and there are no atomics, so the call is deterministic,
+ * graph-capture safe, and clip b's result does not depend on B.  No row outside [0, B*S) is read
+ * (no row padding needed).  r_out may be r_in; work may alias neither.
+ */
+int vc_attention_rollout_step(const uint16_t* qkv, int64_t ld, const float* lse, const float* r_in, int64_t B,
+                              int64_t S, int64_t H, int64_t head_dim, float alpha, float* work, int64_t work_elems,
+                              float* r_out, hipStream_t stream);
+
+/*
  * Attention backward (autograd of eager_attention_forward, TF5/models/vivit/modeling_vivit.py:
  * 149-174).  qkv: the forward's q'|k|v rows (q' = q*scale*log2 e, q_prescaled); out: the forward
  * output O; dout: dL/dO (same layout as out); lse from vc_attention_fwd_lse; delta: caller

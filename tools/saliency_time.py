@@ -1,0 +1,123 @@
+"""Timing of ViViT saliency (VivitForVideoClassification.explain) against the plain forward: ViViT-B/16x2,
+32 x 224^2, synthetic weights and clips, B = 1 and 4.
+
+  python tools/saliency_time.py [--out profiles/saliency_time.json] [--reps 15] [--warmup 3]
+
+Per batch size, each the median of `--reps` calls between device events after `--warmup` calls:
+
+  forward_ms          the plain eager forward (`forward_logits`, one stream, no graph replay; the last layer
+                      for the CLS rows only, as inference runs it);
+  forward_full_ms     the same with every layer over every token (cls_only_last_layer = False), the arithmetic
+                      explain's forward runs;
+  explain_rollout_ms  explain("rollout"): that full forward with the lse-storing attention kernel, the twelve
+                      rollout steps, the [B, S] copy to the host and the host normalisation;
+  rollout_steps_ms    the twelve ops.attention_rollout_step calls alone, on the buffers explain kept;
+  forward_after_ms    the plain forward again at the end: its drift is the margin of the comparison.
+
+The steps' algorithmic work (2 S^2 64 flop and S^2 exp2 per clip, head and layer) is recorded with the rate it
+gives.  A GPU is required: there is no CPU path.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import statistics
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+BATCHES = (1, 4)
+DEV = "cuda"
+
+
+def _time(fn) -> float:
+    """one call between device events, in milliseconds"""
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    fn()
+    e1.record()
+    e1.synchronize()
+    return e0.elapsed_time(e1)
+
+
+def _median(fn, reps: int, warmup: int) -> float:
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    return statistics.median(_time(fn) for _ in range(reps))
+
+
+def main() -> int:
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "saliency_time.json"))
+    ap.add_argument("--reps", type=int, default=15)
+    ap.add_argument("--warmup", type=int, default=3)
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("saliency_time.py needs a GPU")
+
+    from vclip_amd import ops
+    from vclip_amd.build import source_hash
+    from vclip_amd.vivit import create_model
+    from vclip_amd.weights import make_synthetic_clips
+
+    model = create_model(num_frames=32, device=DEV)
+    c = model.config
+    Hn, nl = c.num_attention_heads, c.num_hidden_layers
+    res = {"model": "ViViT-B/16x2 32 x 224^2", "reps": a.reps, "warmup": a.warmup, "build": source_hash(),
+           "device": torch.cuda.get_device_name(0), "batches": {}}
+    for B in BATCHES:
+        pix = torch.from_numpy(make_synthetic_clips(B, 32, 224, seed=1)).to(DEV)
+        _, S, _, _ = model.geometry(B)
+
+        def forward():
+            model.forward_logits(pix)
+
+        def forward_full():
+            model.cls_only_last_layer = False
+            try:
+                model.forward_logits(pix)
+            finally:
+                model.cls_only_last_layer = True
+
+        def explain():
+            model.explain(pix, method="rollout")
+
+        r = {"S": S, "forward_ms": _median(forward, a.reps, a.warmup),
+             "forward_full_ms": _median(forward_full, a.reps, a.warmup),
+             "explain_rollout_ms": _median(explain, a.reps, a.warmup)}
+        buf = model._explain_buffers(B, pix.device)  # as the last explain left them
+
+        def steps():
+            r_in = buf["seed"]
+            for k, li in enumerate(reversed(range(nl))):
+                r_out = buf["r"][k & 1]
+                ops.attention_rollout_step(buf["QKV"][li], buf["LSE"][li], r_in, B, S, Hn, 0.5, buf["work"], r_out)
+                r_in = r_out
+
+        r["rollout_steps_ms"] = _median(steps, a.reps, a.warmup)
+        r["forward_after_ms"] = _median(forward, a.reps, a.warmup)
+        flop, exps = 2.0 * S * S * 64 * Hn * nl * B, 1.0 * S * S * Hn * nl * B
+        r["rollout_steps_flop"], r["rollout_steps_exp2"] = flop, exps
+        r["rollout_steps_tflops"] = flop / (r["rollout_steps_ms"] * 1e-3) / 1e12
+        r["rollout_steps_gexp2_per_s"] = exps / (r["rollout_steps_ms"] * 1e-3) / 1e9
+        r["explain_over_forward"] = r["explain_rollout_ms"] / r["forward_ms"]
+        res["batches"][str(B)] = r
+        print(f"B = {B}: forward {r['forward_ms']:.2f} ms (after {r['forward_after_ms']:.2f}), full forward "
+              f"{r['forward_full_ms']:.2f} ms, explain(rollout) {r['explain_rollout_ms']:.2f} ms, {nl} rollout steps "
+              f"{r['rollout_steps_ms']:.2f} ms ({r['rollout_steps_tflops']:.1f} TFLOP/s, "
+              f"{r['rollout_steps_gexp2_per_s']:.0f} G exp2/s)", flush=True)
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+    print(json.dumps({"out": a.out}))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
