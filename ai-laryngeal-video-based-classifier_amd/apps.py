@@ -213,7 +213,8 @@ FAMILIES = {
 
 VIVIT_SALIENCY_HELP = (
     "absent (default): the label only, as the reference.  rollout: attention rollout of the CLS token over every "
-    "layer (VivitForVideoClassification.explain); cls_attention: the last layer's head-mean CLS attention.  Writes "
+    "layer (VivitForVideoClassification.explain); cls_attention: the last layer's head-mean CLS attention; "
+    "grad_rollout: the class-specific gradient-weighted rollout (Chefer et al. 2021) for --saliency_class.  Writes "
     "<video>_saliency.npy (f32 [T/kt, H/kh, W/kw], sums to 1) beside the result JSON, which gains a \"saliency\" "
     "object with each tubelet's importance and the source-frame indices it covers.")
 
@@ -238,8 +239,12 @@ def build_parser(fam: Family, inference: bool):
             p.add_argument("--visualize", action="store_true")
         if fam.name == "vivit":
             # not in the reference, whose HF model can return its attentions: which tubelets produced the label
-            p.add_argument("--saliency", type=str, default=None, choices=["rollout", "cls_attention"],
+            p.add_argument("--saliency", type=str, default=None, choices=["rollout", "cls_attention", "grad_rollout"],
                            help=VIVIT_SALIENCY_HELP)
+            p.add_argument("--saliency_class", type=int, default=None,
+                           help="with --saliency grad_rollout: the class index whose evidence is mapped (absent: the "
+                                "predicted class); the result JSON's \"saliency\" object names it as target_class / "
+                                "target_label")
         return p
     required = fam.name in ("swin", "resnet3d")
     p.add_argument("--data_dir", type=str, required=True)
@@ -470,13 +475,19 @@ def run_inference(fam_name, argv=None):
     if fam_name == "lstm":
         return run_inference_lstm(argv)
     fam = FAMILIES[fam_name]
-    args = build_parser(fam, inference=True).parse_args(argv)
+    parser = build_parser(fam, inference=True)
+    args = parser.parse_args(argv)
+    saliency_class = getattr(args, "saliency_class", None)
+    if saliency_class is not None and args.saliency != "grad_rollout":
+        parser.error("--saliency_class needs --saliency grad_rollout")
     exp = ExperimentLogger(args.log_dir, prefix=f"{fam.prefix}-inference")
     logger = exp.get_logger()
     device = _device()
     from .checkpoint import load_reference_checkpoint
     ck, sd = load_reference_checkpoint(args.model_path, vivit_keys=fam.name == "vivit")
     id2label = {int(k): v for k, v in (ck.get("id2label") or {0: "non-referral", 1: "referral"}).items()}
+    if saliency_class is not None and saliency_class not in id2label:
+        parser.error(f"--saliency_class {saliency_class} is not one of the checkpoint's labels {sorted(id2label)}")
     class_labels = [id2label[i] for i in sorted(id2label)]
     args.num_classes = len(class_labels)
     if fam.name in ("vivit", "timesformer"):
@@ -526,7 +537,10 @@ def run_inference(fam_name, argv=None):
     out.mkdir(parents=True, exist_ok=True)
     if saliency:
         # the label above is the ordinary forward's, the same with and without the flag; the map is explain's
-        ex = model.explain(x, method=saliency)
+        if saliency == "grad_rollout":  # class-specific: the asked class, or the label printed above
+            ex = model.explain(x, method=saliency, target=pred if saliency_class is None else saliency_class)
+        else:
+            ex = model.explain(x, method=saliency)
         sal = ex.saliency[0].numpy()
         kt = model.config.tubelet_size[0]
         npy = f"{Path(args.video_path).stem}_saliency.npy"
@@ -534,6 +548,8 @@ def run_inference(fam_name, argv=None):
         res["saliency"] = {"method": saliency, "file": npy, "shape": list(sal.shape),
                            "temporal_importance": [float(v) for v in ex.temporal[0]],
                            "tubelet_frame_indices": [frame_idx[i:i + kt] for i in range(0, len(frame_idx), kt)]}
+        if ex.target is not None:
+            res["saliency"].update(target_class=ex.target[0], target_label=id2label[ex.target[0]])
         logger.info(f"Saliency ({saliency}): {out / npy}, most important tubelet {int(ex.temporal[0].argmax())}")
     with open(out / f"{Path(args.video_path).stem}_result.json", "w") as f:
         json.dump(res, f, indent=4)

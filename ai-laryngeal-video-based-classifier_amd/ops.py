@@ -829,6 +829,31 @@ def attention_rollout_step(qkv: torch.Tensor, lse: torch.Tensor, r_in: torch.Ten
     return r_out
 
 
+def attention_grad_rollout_step(qkv: torch.Tensor, dout: torch.Tensor, lse: torch.Tensor, r_in: torch.Tensor, B: int,
+                                S: int, H: int, alpha: float, beta: float, work: torch.Tensor,
+                                r_out: torch.Tensor) -> torch.Tensor:
+    """One gradient-weighted rollout step of the CLS row (vc_attention_grad_rollout_step): r_out = alpha *
+    mean_h(max(P_h * dP_h, 0)^T r_in) + beta * r_in, P_h as attention_rollout_step's and dP_h[i][j] = dout_h[i] . v_j
+    with dout bf16 [>= B*S, >= H*64] (head h at columns 64h, attention_bwd's `dout`).  work from
+    attention_rollout_work."""
+    _dev(qkv, dout, lse, r_in, work, r_out)
+    _need(lse.dtype == torch.float32 and lse.is_contiguous() and lse.numel() >= B * H * S, "lse: f32 [B*H*S]")
+    _need(qkv.dtype == torch.bfloat16 and qkv.dim() == 2 and qkv.stride(1) == 1,
+          "attention_grad_rollout_step: qkv bf16 rows")
+    _need(qkv.shape[1] >= 3 * H * 64 and qkv.shape[0] >= B * S, "attention_grad_rollout_step: qkv rows / columns")
+    _need(dout.dtype == torch.bfloat16 and dout.dim() == 2 and dout.stride(1) == 1,
+          "attention_grad_rollout_step: dout bf16 rows")
+    _need(dout.shape[1] >= H * 64 and dout.shape[0] >= B * S, "attention_grad_rollout_step: dout rows / columns")
+    for t, nm in ((r_in, "r_in"), (r_out, "r_out")):
+        _need(t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (B, S),
+              f"attention_grad_rollout_step: {nm} f32 [B, S]")
+    _need(work.dtype == torch.float32 and work.is_contiguous() and work.numel() >= B * H * S,
+          "attention_grad_rollout_step work: contiguous f32 [B*H*S]")
+    _lib.call("vc_attention_grad_rollout_step", _p(qkv), qkv.stride(0), _p(dout), dout.stride(0), _p(lse), _p(r_in), B,
+              S, H, 64, float(alpha), float(beta), _p(work), work.numel(), _p(r_out), _stream(qkv))
+    return r_out
+
+
 def attention_bwd(qkv: torch.Tensor, out: torch.Tensor, dout: torch.Tensor, lse: torch.Tensor, delta: torch.Tensor,
                   B: int, S: int, H: int, dqkv: torch.Tensor, stream2: torch.cuda.Stream | None = None) -> torch.Tensor:
     """dqkv (q part = dL/dq' of the stored pre-scaled q', then dk, dv) of the joint attention.

@@ -20,6 +20,7 @@ from __future__ import annotations
 import functools
 import json
 import math
+import operator
 from collections import OrderedDict
 
 import numpy as np
@@ -27,6 +28,7 @@ import torch
 
 from . import ops, streams
 from .streams import GraphReplay
+from .vivit_explain import GradRolloutEngine
 from .vivit_train import FlatLayout, TrainEngine, VivitTrainFn
 from .weights import vivit_param_shapes
 
@@ -78,11 +80,13 @@ class VivitConfig:
 class Explanation:
     """What VivitForVideoClassification.explain returns: `logits` f32 [B, labels] on the device;
     `token_relevance` f32 [B, S] (column 0 is CLS), `saliency` f32 [B, T/kt, H/kh, W/kw] (the patch tokens'
-    relevance divided by its per-clip sum) and `temporal` f32 [B, T/kt] (saliency summed over space) on the host."""
+    relevance divided by its per-clip sum) and `temporal` f32 [B, T/kt] (saliency summed over space) on the host.
+    `target`: the B class indices a class-specific method ("grad_rollout") explained, None for the others."""
 
-    def __init__(self, logits, token_relevance, saliency, temporal, method):
+    def __init__(self, logits, token_relevance, saliency, temporal, method, target=None):
         self.logits, self.token_relevance, self.saliency, self.temporal = logits, token_relevance, saliency, temporal
         self.method = method
+        self.target = target
 
 
 class ClassifierOutput:
@@ -135,6 +139,7 @@ class VivitForVideoClassification(torch.nn.Module):
         self._ws = {}
         self._ws_used = []
         self._explain_ws = {}  # explain()'s own buffers per (B, device): not in _ws, which captured graphs hold on to
+        self._explain_grad = {}  # explain(method="grad_rollout")'s engine per (B, device) (vivit_explain.py)
         self._streams = None
         self.concurrent_streams = None  # None / 1: one stream; n > 1: batch split over n HIP streams
         # HIP stream priority per part (lower is higher) of the eager forward's part streams, an A/B hook;
@@ -210,6 +215,7 @@ class VivitForVideoClassification(torch.nn.Module):
         self._packed = None
         self._ws = {}
         self._explain_ws = {}
+        self._explain_grad = {}
         self._streams = None
         self._graphs.clear()
         return out
@@ -648,7 +654,7 @@ class VivitForVideoClassification(torch.nn.Module):
 
 
     # ---- explain ------------------------------------------------------------------
-    EXPLAIN_METHODS = ("rollout", "cls_attention")
+    EXPLAIN_METHODS = ("rollout", "cls_attention", "grad_rollout")
 
     def _explain_buffers(self, B, device):
         key = (B, str(device))
@@ -666,8 +672,61 @@ class VivitForVideoClassification(torch.nn.Module):
                                          work=ops.attention_rollout_work(B, S, Hn, device))
         return self._explain_ws[key]
 
+    def _explain_grad_engine(self, B, device):
+        key = (B, str(device))
+        if key not in self._explain_grad:
+            self._explain_grad = {}  # one batch size at a time: the engine keeps every layer's activations
+            self._explain_grad[key] = GradRolloutEngine(self, B, device)
+        return self._explain_grad[key]
+
+    def _explain_targets(self, target):
+        """`target` of explain checked against the labels: (None or a list of class indices, whether it was one int
+        for every clip)"""
+        if target is None:
+            return None, False
+        nl = self.config.num_labels
+        if isinstance(target, torch.Tensor):
+            if target.is_floating_point() or target.dtype == torch.bool:
+                raise ValueError("explain: target must hold integers")
+            target = target.tolist()
+        if isinstance(target, bool):
+            raise ValueError("explain: target must be None, an int or a sequence of B ints")
+        scalar = not isinstance(target, (list, tuple, np.ndarray))
+        try:
+            target = [operator.index(target)] if scalar else [operator.index(t) for t in target]
+        except TypeError:
+            raise ValueError("explain: target must be None, an int or a sequence of B ints") from None
+        if any(not 0 <= t < nl for t in target):
+            raise ValueError(f"explain: target {target} out of range for {nl} labels")
+        return target, scalar
+
+    def _explain_grad_rollout(self, pix, target, scalar_target) -> Explanation:
+        """explain(method="grad_rollout") past the argument checks: pix f32 contiguous on the GPU, target from
+        _explain_targets"""
+        c = self.config
+        B, T, _, H, W = pix.shape
+        if target is not None:
+            target = target * B if scalar_target else target
+            if len(target) != B:
+                raise ValueError(f"explain: target has {len(target)} entries for {B} clips")
+        eng = self._explain_grad_engine(B, pix.device)
+        logits = eng.forward(pix).clone()
+        if target is None:
+            target = logits.argmax(dim=1).tolist()
+        rel = eng.backward_rollout(target).cpu()  # the one copy; the rest is host bookkeeping on [B, S]
+        kt, kh, kw = c.tubelet_size
+        patch = rel[:, 1:].double()
+        total = patch.sum(dim=1, keepdim=True)
+        if not bool((total > 0).all()):
+            raise RuntimeError(f"explain: grad_rollout found no positive gradient-weighted attention for target "
+                               f"{target}: the patch relevances of clip(s) "
+                               f"{[b for b in range(B) if not total[b, 0] > 0]} sum to 0")
+        sal = (patch / total).float().reshape(B, T // kt, H // kh, W // kw)
+        return Explanation(logits, rel, sal, sal.sum(dim=(2, 3)), method="grad_rollout", target=target)
+
     @torch.no_grad()
-    def explain(self, pixel_values: torch.Tensor, method: str = "rollout", residual: float = 0.5) -> Explanation:
+    def explain(self, pixel_values: torch.Tensor, method: str = "rollout", residual: float = 0.5,
+                target=None) -> Explanation:
         """The logits and which tokens produced them: attention rollout (Abnar & Zuidema 2020) of the CLS row.
 
         method "rollout": r = e_CLS, then for layers L .. 1  r <- residual * mean_h(A_h)^T r + (1 - residual) * r,
@@ -681,10 +740,25 @@ class VivitForVideoClassification(torch.nn.Module):
         (184 MB at B = 1 with the row padding).  The forward's workspaces, graphs and logits are untouched.
         The [B, S] result is copied to the host once; normalisation and the spatial sum happen there.
         Refuses (no fallback): training mode, CPU tensors, compute_dtype fp16 (the lse forward is bf16-only),
-        precise_layers > 0, head_dim != 64."""
+        precise_layers > 0, head_dim != 64.
+
+        method "grad_rollout" is class-specific where the two above are not: the gradient-weighted rollout of
+        Chefer, Gur & Wolf (2021), r = e_CLS, then for layers L .. 1  r <- r + mean_h(max(dy_t/dA_h * A_h, 0))^T r
+        with y_t the logit of `target`: None = per clip the argmax of the logits this call computed, an int = that
+        class for every clip, or B ints (sequence or tensor); out of range, or given with another method, is a
+        ValueError.  `residual` is not used by this method.  It runs a forward that keeps what a backward needs
+        and the train step's data-gradient chain without any weight gradient (vivit_explain.py), each layer's
+        ops.attention_grad_rollout_step as soon as its dO exists; `logits` are that forward's and
+        Explanation.target the B classes explained.  Its buffers (every layer's residual stream, q|k|v, attention
+        output, lse and pre-GELU hidden state, and transposed bf16 weights) are cached for one (B, device).  A clip
+        whose patch relevances sum to 0 (no positive product anywhere) raises RuntimeError.  Refuses what the
+        other methods refuse, and a hidden_act that is not a tanh GELU."""
         c = self.config
         if method not in self.EXPLAIN_METHODS:
             raise ValueError(f"explain: method must be one of {self.EXPLAIN_METHODS}, not {method!r}")
+        if target is not None and method != "grad_rollout":
+            raise ValueError(f"explain: target is for method 'grad_rollout', not {method!r}")
+        target, scalar_target = self._explain_targets(target)
         if not 0.0 < float(residual) <= 1.0:
             raise ValueError(f"explain: residual must be in (0, 1], not {residual}")
         if self.training:
@@ -704,6 +778,8 @@ class VivitForVideoClassification(torch.nn.Module):
         if T != c.num_frames or H != c.image_size or W != c.image_size or C != c.num_channels:
             raise ValueError(f"pixel_values {tuple(pix.shape)} do not match config "
                              f"(T={c.num_frames}, C={c.num_channels}, {c.image_size}^2)")
+        if method == "grad_rollout":
+            return self._explain_grad_rollout(pix, target, scalar_target)
         _, S, _, _ = self.geometry(B)
         Hn, nl = c.num_attention_heads, c.num_hidden_layers
         buf = self._explain_buffers(B, pix.device)

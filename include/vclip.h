@@ -575,6 +575,24 @@ int vc_attention_rollout_step(const uint16_t* qkv, int64_t ld, const float* lse,
                               float* r_out, hipStream_t stream);
 
 /*
+ * One step of the class-specific, gradient-weighted rollout of the CLS row (csrc/attention_rollout.hip;
+ * Chefer, Gur & Wolf 2021, "Generic Attention-model Explainability", the self-attention rule).  With
+ * P_h as above and dP_h[i][j] = dO_h[i] . v_j the gradient of the target logit with respect to
+ * P_h[i][j] (dout: dL/dO of this layer's attention, bf16 [>= B*S rows, >= H*64], head h at columns
+ * 64h, leading dimension lddo -- the `dout` of vc_attention_bwd; bf16 MFMA, fp32 accumulation):
+ *     u[b][j]     = (1/H) sum_h sum_i r_in[b][i] * max(P_h[i][j] * dP_h[i][j], 0)
+ *     r_out[b][j] = alpha * u[b][j] + beta * r_in[b][j]
+ * alpha = beta = 1 from r_in = e_CLS, last layer first, is the CLS row of R <- R + mean_h(max(grad A
+ * . A, 0)) R.  Same contract as vc_attention_rollout_step: head_dim 64, work_elems >= B*H*S, two
+ * launches, no atomics, deterministic, batch-invariant; no row of qkv or dout outside [0, B*S) is
+ * read.  r_out may be r_in; work may alias neither.
+ */
+int vc_attention_grad_rollout_step(const uint16_t* qkv, int64_t ld, const uint16_t* dout, int64_t lddo,
+                                   const float* lse, const float* r_in, int64_t B, int64_t S, int64_t H,
+                                   int64_t head_dim, float alpha, float beta, float* work, int64_t work_elems,
+                                   float* r_out, hipStream_t stream);
+
+/*
  * Attention backward (autograd of eager_attention_forward, TF5/models/vivit/modeling_vivit.py:
  * 149-174).  qkv: the forward's q'|k|v rows (q' = q*scale*log2 e, q_prescaled); out: the forward
  * output O; dout: dL/dO (same layout as out); lse from vc_attention_fwd_lse; delta: caller

@@ -14,8 +14,19 @@ Per batch size, each the median of `--reps` calls between device events after `-
   rollout_steps_ms    the twelve ops.attention_rollout_step calls alone, on the buffers explain kept;
   forward_after_ms    the plain forward again at the end: its drift is the margin of the comparison.
 
-The steps' algorithmic work (2 S^2 64 flop and S^2 exp2 per clip, head and layer) is recorded with the rate it
-gives.  A GPU is required: there is no CPU path.
+The class-specific method, in the same run:
+
+  explain_grad_rollout_ms      explain("grad_rollout", target=0): the activation-keeping forward, the data-gradient
+                               chain with a gradient-weighted rollout step per layer, the copy and the host part;
+  grad_rollout_steps_ms        the twelve ops.attention_grad_rollout_step calls alone, on the buffers its engine
+                               kept (dO is the last one the chain left: the work does not depend on its values);
+  grad_rollout_extra_bytes     peak device memory of the first such call above what was allocated before it (the
+                               engine's buffers and transposed weights included);
+  train_fwd_bwd_ms             one forward plus backward of the train step (every weight gradient, its side
+                               streams) on a second model, measured after everything else: what explain should undercut.
+
+The steps' algorithmic work (2 S^2 64 flop and S^2 exp2 per clip, head and layer; twice the flop for the
+gradient-weighted step) is recorded with the rate it gives.  A GPU is required: there is no CPU path.
 """
 from __future__ import annotations
 
@@ -106,11 +117,54 @@ def main() -> int:
         r["rollout_steps_tflops"] = flop / (r["rollout_steps_ms"] * 1e-3) / 1e12
         r["rollout_steps_gexp2_per_s"] = exps / (r["rollout_steps_ms"] * 1e-3) / 1e9
         r["explain_over_forward"] = r["explain_rollout_ms"] / r["forward_ms"]
+
+        def explain_grad():
+            model.explain(pix, method="grad_rollout", target=0)
+
+        model._explain_grad = {}  # the other batch size's engine must not count as already allocated
+        torch.cuda.synchronize()
+        base = torch.cuda.memory_allocated()
+        torch.cuda.reset_peak_memory_stats()
+        explain_grad()
+        torch.cuda.synchronize()
+        r["grad_rollout_extra_bytes"] = torch.cuda.max_memory_allocated() - base
+        r["explain_grad_rollout_ms"] = _median(explain_grad, a.reps, a.warmup)
+        eng = model._explain_grad_engine(B, pix.device)  # as the last explain left it
+
+        def grad_steps():
+            r_in = eng.seed
+            for k, li in enumerate(reversed(range(nl))):
+                r_out = eng.r[k & 1]
+                ops.attention_grad_rollout_step(eng.QKV[li], eng.dO, eng.LSE[li], r_in, B, S, Hn, 1.0, 1.0, eng.work,
+                                                r_out)
+                r_in = r_out
+
+        r["grad_rollout_steps_ms"] = _median(grad_steps, a.reps, a.warmup)
+        r["grad_rollout_steps_flop"] = 2 * flop
+        r["grad_rollout_steps_tflops"] = 2 * flop / (r["grad_rollout_steps_ms"] * 1e-3) / 1e12
+        r["grad_rollout_steps_gexp2_per_s"] = exps / (r["grad_rollout_steps_ms"] * 1e-3) / 1e9
+        r["grad_step_over_plain_step"] = r["grad_rollout_steps_ms"] / r["rollout_steps_ms"]
         res["batches"][str(B)] = r
         print(f"B = {B}: forward {r['forward_ms']:.2f} ms (after {r['forward_after_ms']:.2f}), full forward "
               f"{r['forward_full_ms']:.2f} ms, explain(rollout) {r['explain_rollout_ms']:.2f} ms, {nl} rollout steps "
               f"{r['rollout_steps_ms']:.2f} ms ({r['rollout_steps_tflops']:.1f} TFLOP/s, "
-              f"{r['rollout_steps_gexp2_per_s']:.0f} G exp2/s)", flush=True)
+              f"{r['rollout_steps_gexp2_per_s']:.0f} G exp2/s); explain(grad_rollout) "
+              f"{r['explain_grad_rollout_ms']:.2f} ms, {nl} grad-rollout steps {r['grad_rollout_steps_ms']:.2f} ms "
+              f"({r['grad_rollout_steps_tflops']:.1f} TFLOP/s), peak extra memory "
+              f"{r['grad_rollout_extra_bytes'] / 1e6:.0f} MB", flush=True)
+    # the train step's forward + backward, last: it moves its model's parameters into the flat training buffers
+    model._explain_grad = {}
+    trainee = create_model(num_frames=32, device=DEV).train()
+    for B in BATCHES:
+        pix = torch.from_numpy(make_synthetic_clips(B, 32, 224, seed=1)).to(DEV)
+
+        def fwd_bwd():
+            trainee(pixel_values=pix).logits[:, 0].sum().backward()
+
+        r = res["batches"][str(B)]
+        r["train_fwd_bwd_ms"] = _median(fwd_bwd, a.reps, a.warmup)
+        r["explain_grad_over_train_fwd_bwd"] = r["explain_grad_rollout_ms"] / r["train_fwd_bwd_ms"]
+        print(f"B = {B}: train forward + backward {r['train_fwd_bwd_ms']:.2f} ms", flush=True)
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as f:
         json.dump(res, f, indent=1)
