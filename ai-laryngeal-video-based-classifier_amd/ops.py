@@ -854,6 +854,27 @@ def attention_grad_rollout_step(qkv: torch.Tensor, dout: torch.Tensor, lse: torc
     return r_out
 
 
+def temporal_rollout_step(qkv: torch.Tensor, r_frame_in: torch.Tensor, B: int, P: int, T: int, H: int, alpha: float,
+                          r_clip_out: torch.Tensor, r_frame_out: torch.Tensor | None = None) -> torch.Tensor:
+    """The temporal half of one rollout step through a TimeSformer layer (vc_temporal_rollout_step): per (clip,
+    patch) y = alpha * mean_h(P_h^T x) + (1 - alpha) * x over the patch's T frames, x = r_frame_in[b*T + t, 1 + p],
+    P_h recomputed from the temporal qkv bf16 [>= B*(1+P*T), >= 3*H*64] (clip layout, q pre-scaled).  r_frame_in
+    f32 [B*T, 1+P] (the spatial step's output) -> r_clip_out f32 [B, 1+P*T] (column 0: the sum of the T CLS slots)
+    and, if given, r_frame_out f32 [B*T, 1+P], the same values spread for the next layer's spatial step."""
+    outs = (r_clip_out,) if r_frame_out is None else (r_clip_out, r_frame_out)
+    _dev(qkv, r_frame_in, *outs)
+    _need(qkv.dtype == torch.bfloat16 and qkv.dim() == 2 and qkv.stride(1) == 1, "temporal_rollout_step: qkv bf16 rows")
+    _need(qkv.shape[1] >= 3 * H * 64 and qkv.shape[0] >= B * (1 + P * T), "temporal_rollout_step: qkv rows / columns")
+    _need(T <= 32, "temporal_rollout_step: T <= 32")
+    for t, nm, shape in ((r_frame_in, "r_frame_in", (B * T, 1 + P)), (r_clip_out, "r_clip_out", (B, 1 + P * T)),
+                         (r_frame_out, "r_frame_out", (B * T, 1 + P))):
+        _need(t is None or (t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == shape),
+              f"temporal_rollout_step: {nm} f32 {list(shape)}")
+    _lib.call("vc_temporal_rollout_step", _p(qkv), qkv.stride(0), _p(r_frame_in), B, P, T, H, 64, float(alpha),
+              _p(r_clip_out), None if r_frame_out is None else _p(r_frame_out), _stream(qkv))
+    return r_clip_out
+
+
 def attention_bwd(qkv: torch.Tensor, out: torch.Tensor, dout: torch.Tensor, lse: torch.Tensor, delta: torch.Tensor,
                   B: int, S: int, H: int, dqkv: torch.Tensor, stream2: torch.cuda.Stream | None = None) -> torch.Tensor:
     """dqkv (q part = dL/dq' of the stored pre-scaled q', then dk, dv) of the joint attention.

@@ -118,6 +118,7 @@ class TimesformerForVideoClassification(torch.nn.Module):
         self._packed = None
         self._ws = {}
         self._ws_used = []
+        self._explain_ws = {}  # explain()'s own buffers per (B, device): not in _ws, which captured graphs hold on to
 
     def state_dict(self, *a, **k):
         return OrderedDict((n, self.params[n.replace(".", "__")].detach()) for n in self._names)
@@ -279,7 +280,10 @@ class TimesformerForVideoClassification(torch.nn.Module):
         from .streams import run_split
         return run_split(self, pix, ns, self._forward_part, c.num_labels, prepare=lambda: self._pack(pix.device))
 
-    def _forward_part(self, pix: torch.Tensor, part: int, out=None) -> torch.Tensor:
+    def _forward_part(self, pix: torch.Tensor, part: int, out=None, keep=None) -> torch.Tensor:
+        """keep (explain only): {"QKV_t": [L, Mpad, 3D], "QKV_s": [L, Mpad, 3D], "LSE_s": [L, B*T*H*(1+P)]} -- layer
+        i's temporal and spatial q|k|v go to keep["QKV_t"][i] / keep["QKV_s"][i] instead of the shared buffer and
+        its spatial attention is ops.attention_fwd_lse, which stores the base-2 log-sum-exp in keep["LSE_s"][i]."""
         c = self.config
         B = pix.shape[0]
         pk = self._pack(pix.device)
@@ -304,8 +308,10 @@ class TimesformerForVideoClassification(torch.nn.Module):
         scale = 1.0 / math.sqrt(c.hidden_size // Hn)
         pcfg = -1 if self.proj_cfg is None else self.proj_cfg
         gc = self.gemm_cfg
-        for L in pk["layers"]:
+        for li, L in enumerate(pk["layers"]):
             # temporal branch (clip layout)
+            if keep is not None:
+                QKV = keep["QKV_t"][li]
             tm("layernorm_kernel", "layernorm", Mc * D * 6, "byte", ops.layernorm, X, L["lnt_g"], L["lnt_b"], eps, Hc,
                m=B * S)
             ops.gemm(Hc, L["w_qkv_t"], L["b_qkv_t"], "bias", QKV, cfg=gc.get("qkv_temporal", -1), flop=2.0 * Mc * 3 * D * D, op="qkv_temporal")
@@ -315,13 +321,18 @@ class TimesformerForVideoClassification(torch.nn.Module):
             # spatial branch (frame layout): X += temporal output, LayerNorm in the frame layout
             tm("tsf_add_ln_kernel", "add_layernorm", Mc * D * (4 + 2 + 4) + Mf * D * 2, "byte",
                ops.divided_add_layernorm, X, Yb, B, P, T, L["ln1_g"], L["ln1_b"], eps, "temporal_to_spatial", Hf)
+            if keep is not None:
+                QKV = keep["QKV_s"][li]
             ops.gemm(Hf, L["w_qkv_s"], L["b_qkv_s"], "bias", QKV, cfg=gc.get("qkv_spatial", -1), flop=2.0 * Mf * 3 * D * D, op="qkv_spatial")
             ev = self.kernel_events
             if ev is not None:  # recorded on the current stream, the one the kernel runs on
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 e0.record()
-            tm("attn_short_d64_kernel", "spatial_attention", 4.0 * (1 + P) * (1 + P) * 64 * Hn * B * T, "flop",
-               ops.attention, QKV, B * T, 1 + P, Hn, scale, O, q_prescaled=True)
+            if keep is not None:
+                ops.attention_fwd_lse(QKV, B * T, 1 + P, Hn, O, keep["LSE_s"][li], scale=scale, q_prescaled=True)
+            else:
+                tm("attn_short_d64_kernel", "spatial_attention", 4.0 * (1 + P) * (1 + P) * 64 * Hn * B * T, "flop",
+                   ops.attention, QKV, B * T, 1 + P, Hn, scale, O, q_prescaled=True)
             if ev is not None:
                 e1.record()
                 # flop, algorithmic bytes (q, k, v read and the output written once: 4 x 64 x 2 B
@@ -336,6 +347,97 @@ class TimesformerForVideoClassification(torch.nn.Module):
         return ops.cls_head(X, B, S, pk["lnf_g"], pk["lnf_b"], eps, pk["w_cls"], pk["b_cls"],
                             out=ws["logits"] if out is None else out)
 
+    # ---- explain ------------------------------------------------------------------
+    EXPLAIN_METHODS = ("rollout", "cls_attention")
+
+    def _explain_buffers(self, B, device):
+        key = (B, str(device))
+        if key not in self._explain_ws:
+            if len(self._explain_ws) >= 2:
+                self._explain_ws = {}
+            c = self.config
+            P, T, S, Mpad, _ = self.geometry(B)
+            Hn, nl = c.num_attention_heads, c.num_hidden_layers
+            seed = torch.zeros(B * T, 1 + P, dtype=torch.float32)
+            seed[:, 0] = 1.0 / T  # e_CLS in the frame layout, made on the host: every frame's slot 0 holds r_CLS / T
+            f = lambda *s: torch.zeros(s, dtype=torch.float32, device=device)  # noqa: E731
+            q = lambda: torch.zeros(nl, Mpad, 3 * c.hidden_size, dtype=torch.bfloat16, device=device)  # noqa: E731
+            self._explain_ws[key] = dict(QKV_t=q(), QKV_s=q(), LSE_s=f(nl, B * T * Hn * (1 + P)), seed=seed.to(device),
+                                         r_frame=(f(B * T, 1 + P), f(B * T, 1 + P)), r_clip=f(B, S),
+                                         work=ops.attention_rollout_work(B * T, 1 + P, Hn, device))
+        return self._explain_ws[key]
+
+    @torch.no_grad()
+    def explain(self, pixel_values: torch.Tensor, method: str = "rollout", residual: float = 0.5):
+        """The logits and which tokens produced them: attention rollout (Abnar & Zuidema 2020) of the CLS row
+        through divided space-time attention.  Returns vivit.Explanation: `logits` f32 [B, labels] on the device;
+        on the host `token_relevance` f32 [B, S] in the clip layout (column 0 is CLS, token (p, t) at 1 + p*T + t),
+        `saliency` f32 [B, T, H/ps, W/ps] (the patch relevances divided by their per-clip sum, token (p, t) at
+        [t, p // gw, p % gw]) and `temporal` f32 [B, T] (saliency summed over space).
+
+        A layer mixes tokens as x <- A_s A_t x (the MLP mixes none), with a = `residual`:
+          temporal  A_t = a * mean_h(A_t[p]) + (1 - a) * I on the T x T block of every patch; the CLS row is the
+                    identity (the temporal branch never updates CLS);
+          spatial   A_s, frame t over [CLS, (0, t) .. (P-1, t)]: a patch row is (1 - a) * e_(p,t) + a * its head-mean
+                    attention row; the CLS row is (1 - a) * e_CLS + a * the mean over the T frames of the per-frame
+                    CLS rows (the model averages the per-frame CLS outputs).
+        method "rollout": r = e_CLS, then for layers L .. 1  r <- (r A_s) A_t.  In the frame layout ([B*T, 1 + P],
+        every frame's slot 0 holding r_CLS / T) the spatial step is ops.attention_rollout_step with B' = B*T and
+        S' = 1 + P; ops.temporal_rollout_step is the temporal step, gathers to the clip layout and spreads the
+        result for the next layer: three launches per layer, and no attention matrix exists at any time.
+        "cls_attention": the spatial step of the last layer alone with a = 1, i.e. CLS (1/T) sum_t A_s^t[0, 0] and
+        patch (p, t) A_s^t[0, 1 + p] / T.
+
+        Runs the ordinary eager forward (no graph replay, no stream split) with the lse-storing spatial attention
+        kernel and keeps every layer's temporal and spatial q|k|v [L, Mpad, 3D] bf16 and the spatial lse in buffers of
+        its own, cached per (B, device): 198 MB at TimeSformer-B 8 x 224^2, B = 1.  The forward's workspaces, graphs
+        and logits are untouched.  The result is copied to the host once; normalisation and the sums happen there.
+        Refuses (no fallback): training mode, CPU tensors, an unknown method (the class-specific "grad_rollout" is
+        ViViT's only), residual outside (0, 1], shapes that do not match the config, B*T*heads > 65535."""
+        from .vivit import Explanation
+        c = self.config
+        if method not in self.EXPLAIN_METHODS:
+            raise ValueError(f"explain: method must be one of {self.EXPLAIN_METHODS}, not {method!r}")
+        if not 0.0 < float(residual) <= 1.0:
+            raise ValueError(f"explain: residual must be in (0, 1], not {residual}")
+        if self.training:
+            raise RuntimeError("explain: inference only; call model.eval() first")
+        if pixel_values is None or pixel_values.device.type != "cuda":
+            raise RuntimeError("explain runs on the GPU only: move pixel_values to cuda")
+        if pixel_values.dim() != 5:
+            raise ValueError(f"pixel_values {tuple(pixel_values.shape)} must be [B, T, C, H, W]")
+        B, T, C, H, W = pixel_values.shape
+        if T != c.num_frames or H != c.image_size or W != c.image_size or C != c.num_channels:
+            raise ValueError(f"pixel_values {tuple(pixel_values.shape)} do not match config "
+                             f"(T={c.num_frames}, C={c.num_channels}, {c.image_size}^2)")
+        Hn, nl = c.num_attention_heads, c.num_hidden_layers
+        if B * T * Hn > 65535:  # the spatial step runs one grid row per (frame, head)
+            raise ValueError(f"explain: B * T * heads = {B * T * Hn} exceeds the rollout step's grid limit of 65535: "
+                             f"at most B = {65535 // (T * Hn)} clips per call")
+        pix = pixel_values.contiguous()
+        if pix.dtype != torch.float32:
+            pix = pix.float()
+        P = self.geometry(B)[0]
+        buf = self._explain_buffers(B, pix.device)
+        logits = self._forward_part(pix, 0, keep=buf).clone()
+        fa, fb = buf["r_frame"]
+        if method == "rollout":
+            r_f, alpha = buf["seed"], float(residual)
+            for li in reversed(range(nl)):
+                ops.attention_rollout_step(buf["QKV_s"][li], buf["LSE_s"][li], r_f, B * T, 1 + P, Hn, alpha, buf["work"], fa)
+                ops.temporal_rollout_step(buf["QKV_t"][li], fa, B, P, T, Hn, alpha, buf["r_clip"], fb if li else None)
+                r_f = fb
+            rel = buf["r_clip"].cpu()  # the one copy; the rest is host bookkeeping on [B, S]
+        else:
+            ops.attention_rollout_step(buf["QKV_s"][nl - 1], buf["LSE_s"][nl - 1], buf["seed"], B * T, 1 + P, Hn, 1.0,
+                                       buf["work"], fa)
+            r_f = fa.cpu().reshape(B, T, 1 + P)  # the one copy; gathered to the clip layout on the host
+            rel = torch.cat([r_f[:, :, 0].sum(dim=1, keepdim=True),
+                             r_f[:, :, 1:].transpose(1, 2).reshape(B, P * T)], dim=1).contiguous()
+        g = c.image_size // c.patch_size
+        patch = rel[:, 1:].double().reshape(B, P, T).transpose(1, 2)  # token (p, t) -> [t, p]
+        sal = (patch / patch.sum(dim=(1, 2), keepdim=True)).float().reshape(B, T, g, g).contiguous()
+        return Explanation(logits, rel, sal, sal.sum(dim=(2, 3)), method)
 
     def _forward_train(self, pix: torch.Tensor) -> torch.Tensor:
         """The TimeSformer forward (TF5/models/timesformer/modeling_timesformer.py:67-145, 332-398,

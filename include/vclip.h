@@ -593,6 +593,30 @@ int vc_attention_grad_rollout_step(const uint16_t* qkv, int64_t ld, const uint16
                                    float* r_out, hipStream_t stream);
 
 /*
+ * The temporal half of one attention-rollout step through a TimeSformer layer (csrc/divided_rollout.hip).
+ * A divided space-time layer mixes tokens as x <- A_s A_t x, so the CLS row of the rollout takes, per
+ * layer and last layer first, r <- (r A_s) A_t: the spatial step is vc_attention_rollout_step on the
+ * frame layout (B' = B*T sequences of S' = 1 + P tokens, every frame's slot 0 holding r_CLS / T), and
+ * this is the temporal step together with the hop between the layouts.  qkv: the layer's TEMPORAL
+ * q'|k|v rows in the clip layout (rows b*(1 + P*T) + 1 + p*T + t, q' = q*scale*log2 e, bf16, head_dim
+ * 64); r_frame_in f32 [B*T, 1 + P], the spatial step's output.  For every (b, p), x[t] = r_frame_in
+ * [b*T + t][1 + p]:
+ *     y[t'] = alpha * (1/H) sum_h sum_t x[t] * P_h[t][t'] + (1 - alpha) * x[t'],
+ *     P_h[t][.] = softmax2(q'_t . k_.) over the patch's T frames, recomputed with the exact maximum
+ *     and sum (no lse input, nothing stored); the temporal branch never updates CLS (identity row):
+ *     c = sum_t r_frame_in[b*T + t][0], summed in t order.
+ * r_clip_out f32 [B, 1 + P*T]: [b][0] = c, [b][1 + p*T + t'] = y[t'].  r_frame_out (may be NULL) f32
+ * [B*T, 1 + P], the next layer's spatial input: [b*T + t'][1 + p] = the same bits, [b*T + t][0] = c / T.
+ * T <= 32 and T*(256*H + 4*H*T + 4) <= 160 KiB of LDS.  One launch, no atomics (heads summed in head
+ * order, then frames in frame order): deterministic, and clip b's result does not depend on B.  The CLS
+ * rows of qkv and its rows past B*(1 + P*T) are never read.  The outputs may alias neither r_frame_in
+ * nor each other.
+ */
+int vc_temporal_rollout_step(const uint16_t* qkv, int64_t ld, const float* r_frame_in, int64_t B, int64_t P,
+                             int64_t T, int64_t H, int64_t head_dim, float alpha, float* r_clip_out,
+                             float* r_frame_out, hipStream_t stream);
+
+/*
  * Attention backward (autograd of eager_attention_forward, TF5/models/vivit/modeling_vivit.py:
  * 149-174).  qkv: the forward's q'|k|v rows (q' = q*scale*log2 e, q_prescaled); out: the forward
  * output O; dout: dL/dO (same layout as out); lse from vc_attention_fwd_lse; delta: caller

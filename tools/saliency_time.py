@@ -27,6 +27,13 @@ The class-specific method, in the same run:
 
 The steps' algorithmic work (2 S^2 64 flop and S^2 exp2 per clip, head and layer; twice the flop for the
 gradient-weighted step) is recorded with the rate it gives.  A GPU is required: there is no CPU path.
+
+  python tools/saliency_time.py --family timesformer [--out profiles/saliency_time_timesformer.json]
+
+times TimesformerForVideoClassification.explain instead: TimeSformer-B, 8 x 224^2, B = 1, the same medians:
+forward_ms, explain_rollout_ms, explain_cls_attention_ms, rollout_steps_ms (the 3 launches per layer alone: the
+spatial step's two and the temporal step's one), temporal_steps_ms (the twelve ops.temporal_rollout_step calls
+alone), forward_after_ms, and the size of the kept q|k|v and lse buffers.
 """
 from __future__ import annotations
 
@@ -62,14 +69,84 @@ def _median(fn, reps: int, warmup: int) -> float:
     return statistics.median(_time(fn) for _ in range(reps))
 
 
+def timesformer(a) -> dict:
+    """TimeSformer-B, 8 x 224^2, B = 1: the plain forward, explain("rollout") and ("cls_attention"), and the rollout's
+    launches alone (per layer the spatial step's two and the temporal step's one) on the buffers explain kept"""
+    from vclip_amd import ops
+    from vclip_amd.build import source_hash
+    from vclip_amd.timesformer import create_model
+    from vclip_amd.weights import make_synthetic_clips
+
+    model = create_model(num_frames=8, device=DEV).eval()
+    c = model.config
+    Hn, nl, B = c.num_attention_heads, c.num_hidden_layers, 1
+    pix = torch.from_numpy(make_synthetic_clips(B, 8, 224, seed=1)).to(DEV)
+    P, T, S, _, _ = model.geometry(B)
+
+    def forward():
+        model.forward_logits(pix)
+
+    def explain():
+        model.explain(pix, method="rollout")
+
+    def explain_cls():
+        model.explain(pix, method="cls_attention")
+
+    r = {"S": S, "P": P, "T": T, "forward_ms": _median(forward, a.reps, a.warmup),
+         "explain_rollout_ms": _median(explain, a.reps, a.warmup),
+         "explain_cls_attention_ms": _median(explain_cls, a.reps, a.warmup)}
+    buf = model._explain_buffers(B, pix.device)  # as the last explain left them
+    fa, fb = buf["r_frame"]
+
+    def steps():
+        r_f = buf["seed"]
+        for li in reversed(range(nl)):
+            ops.attention_rollout_step(buf["QKV_s"][li], buf["LSE_s"][li], r_f, B * T, 1 + P, Hn, 0.5, buf["work"], fa)
+            ops.temporal_rollout_step(buf["QKV_t"][li], fa, B, P, T, Hn, 0.5, buf["r_clip"], fb if li else None)
+            r_f = fb
+
+    def temporal_steps():
+        for li in reversed(range(nl)):
+            ops.temporal_rollout_step(buf["QKV_t"][li], fa, B, P, T, Hn, 0.5, buf["r_clip"], fb)
+
+    r["rollout_steps_ms"] = _median(steps, a.reps, a.warmup)
+    r["temporal_steps_ms"] = _median(temporal_steps, a.reps, a.warmup)
+    r["forward_after_ms"] = _median(forward, a.reps, a.warmup)
+    r["rollout_launches"] = 3 * nl
+    r["kept_qkv_bytes"] = buf["QKV_t"].numel() * 2 + buf["QKV_s"].numel() * 2
+    r["kept_lse_bytes"] = buf["LSE_s"].numel() * 4
+    # per layer 2 (1+P)^2 64 flop per (frame, head) in the spatial step and 2 T^2 64 per (patch, head) in the temporal one
+    r["rollout_steps_flop"] = 2.0 * 64 * Hn * nl * B * (T * (1 + P) ** 2 + P * T * T)
+    r["explain_over_forward"] = r["explain_rollout_ms"] / r["forward_ms"]
+    print(f"TimeSformer-B B = {B}: forward {r['forward_ms']:.2f} ms (after {r['forward_after_ms']:.2f}), explain(rollout) "
+          f"{r['explain_rollout_ms']:.2f} ms, explain(cls_attention) {r['explain_cls_attention_ms']:.2f} ms, "
+          f"{3 * nl} rollout launches {r['rollout_steps_ms']:.3f} ms of which {nl} temporal steps "
+          f"{r['temporal_steps_ms']:.3f} ms; kept q|k|v {r['kept_qkv_bytes'] / 1e6:.0f} MB + lse "
+          f"{r['kept_lse_bytes'] / 1e6:.1f} MB", flush=True)
+    return {"model": "TimeSformer-B 8 x 224^2", "reps": a.reps, "warmup": a.warmup, "build": source_hash(),
+            "device": torch.cuda.get_device_name(0), "batches": {str(B): r}}
+
+
 def main() -> int:
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "saliency_time.json"))
+    ap.add_argument("--family", choices=("vivit", "timesformer"), default="vivit")
+    ap.add_argument("--out", default=None)
     ap.add_argument("--reps", type=int, default=15)
     ap.add_argument("--warmup", type=int, default=3)
     a = ap.parse_args()
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "saliency_time.json" if a.family == "vivit" else
+                             "saliency_time_timesformer.json")
     if not torch.cuda.is_available():
         raise SystemExit("saliency_time.py needs a GPU")
+    if a.family == "timesformer":
+        res = timesformer(a)
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(res, f, indent=1)
+            f.write("\n")
+        print(json.dumps({"out": a.out}))
+        return 0
 
     from vclip_amd import ops
     from vclip_amd.build import source_hash
