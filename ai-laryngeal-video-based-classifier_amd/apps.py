@@ -154,7 +154,8 @@ class Family:
         """Decoded uint8 frames the transform consumes: the sampled frames (ViViT/TimeSformer,
         resized to 224 as dataset.py:271-277), or every frame of the sampled span (Swin/ResNet3D
         `get_clip(idx0/fps, (idxN+1)/fps)`, then UniformTemporalSubsample on the GPU).
-        want_indices (ViViT/TimeSformer): also the source-frame index of each returned frame."""
+        want_indices: also the source-frame index of each frame the model sees (ViViT/TimeSformer: of each returned
+        frame; Swin/ResNet3D: of the num_frames the subsample keeps of the span)."""
         idx = sampler.get_sampling_indices(str(path), src.total_frames)
         if isinstance(idx, tuple):
             idx = idx[0]
@@ -166,7 +167,12 @@ class Family:
                 fr = np.concatenate([fr, np.repeat(fr[-1:], num_frames - len(fr), 0)])
             return (fr[:num_frames], used[:num_frames]) if want_indices else fr[:num_frames]
         lo, hi = int(min(idx)), int(max(idx))
-        return src.read(list(range(lo, hi + 1)))
+        fr = src.read(list(range(lo, hi + 1)))
+        if want_indices:  # the frames of the span that UniformTemporalSubsample keeps (to_model_input)
+            from .preprocess import uniform_temporal_subsample_indices
+            keep = uniform_temporal_subsample_indices(len(fr), num_frames)
+            return fr, [min(lo + int(i), src.total_frames - 1) for i in keep]
+        return fr
 
     def to_model_input(self, frames_u8: torch.Tensor, num_frames, div255=False, train=False):
         """train: the Swin / ResNet3D train chain (RandomShortSideScale, RandomCrop, RandomHorizontalFlip;
@@ -219,7 +225,33 @@ VIVIT_SALIENCY_HELP = (
     "object with each tubelet's importance and the source-frame indices it covers.")
 
 
-def build_parser(fam: Family, inference: bool):
+TIMESFORMER_SALIENCY_HELP = (
+    "absent (default): the label only, as the reference.  rollout: attention rollout of the CLS token through the "
+    "divided space-time attention of every layer (TimesformerForVideoClassification.explain); cls_attention: the last "
+    "layer's head-mean spatial CLS attention.  Writes <video>_saliency.npy (f32 [T, H/ps, W/ps], sums to 1) beside the "
+    "result JSON, which gains a \"saliency\" object with each frame's importance and its source-frame index.")
+SWIN_SALIENCY_HELP = (
+    "absent (default): the label only, as the reference.  rollout: attention rollout from the pooled tokens back "
+    "through every block's shifted-window attention and every PatchMerging (Swin3d.explain).  Writes "
+    "<video>_saliency.npy (f32 [T/2, H/4, W/4], sums to 1) beside the result JSON, which gains a \"saliency\" object "
+    "with each time step's importance and the two source-frame indices it covers.")
+
+
+def _temporal_patch(model) -> int:
+    """sampled frames per time step of the family's saliency map: ViViT's tubelet depth, Swin's patch_size[0],
+    1 for TimeSformer (per-frame patches)"""
+    cfg = getattr(model, "config", None)
+    if cfg is not None and hasattr(cfg, "tubelet_size"):
+        return int(cfg.tubelet_size[0])
+    if isinstance(getattr(model, "cfg", None), dict) and "patch_size" in model.cfg:
+        return int(model.cfg["patch_size"][0])
+    return 1
+
+
+def build_parser(fam: Family, inference: bool, saliency: bool = False):
+    """The folder's reference flags (plus ViViT's --saliency / --saliency_class).  saliency=True, as run_inference
+    builds it: the TimeSformer and Swin inference parsers also get their own --saliency; the two-argument form keeps
+    the flag surface those two families had before their `explain` existed."""
     if fam.name == "lstm":
         return build_parser_lstm(inference)
     p = argparse.ArgumentParser(description=f"{fam.name} video classifier (libvclip, MI355X)")
@@ -245,6 +277,11 @@ def build_parser(fam: Family, inference: bool):
                            help="with --saliency grad_rollout: the class index whose evidence is mapped (absent: the "
                                 "predicted class); the result JSON's \"saliency\" object names it as target_class / "
                                 "target_label")
+        elif fam.name == "timesformer" and saliency:
+            p.add_argument("--saliency", type=str, default=None, choices=["rollout", "cls_attention"],
+                           help=TIMESFORMER_SALIENCY_HELP)
+        elif fam.name == "swin" and saliency:
+            p.add_argument("--saliency", type=str, default=None, choices=["rollout"], help=SWIN_SALIENCY_HELP)
         return p
     required = fam.name in ("swin", "resnet3d")
     p.add_argument("--data_dir", type=str, required=True)
@@ -475,7 +512,7 @@ def run_inference(fam_name, argv=None):
     if fam_name == "lstm":
         return run_inference_lstm(argv)
     fam = FAMILIES[fam_name]
-    parser = build_parser(fam, inference=True)
+    parser = build_parser(fam, inference=True, saliency=True)
     args = parser.parse_args(argv)
     saliency_class = getattr(args, "saliency_class", None)
     if saliency_class is not None and args.saliency != "grad_rollout":
@@ -542,7 +579,7 @@ def run_inference(fam_name, argv=None):
         else:
             ex = model.explain(x, method=saliency)
         sal = ex.saliency[0].numpy()
-        kt = model.config.tubelet_size[0]
+        kt = _temporal_patch(model)
         npy = f"{Path(args.video_path).stem}_saliency.npy"
         np.save(out / npy, sal)
         res["saliency"] = {"method": saliency, "file": npy, "shape": list(sal.shape),

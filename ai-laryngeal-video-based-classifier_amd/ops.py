@@ -875,6 +875,56 @@ def temporal_rollout_step(qkv: torch.Tensor, r_frame_in: torch.Tensor, B: int, P
     return r_clip_out
 
 
+def window_rollout_work(B: int, grid, heads: int, device) -> torch.Tensor:
+    """the f32 scratch of window_rollout_step: three floats per (head, clip, token) -- the per-head partials, and each
+    row's maximum and weight between the step's two passes"""
+    T, H, W = grid
+    return torch.zeros(3 * heads * B * T * H * W, dtype=torch.float32, device=device)
+
+
+def window_rollout_step(qkv: torch.Tensor, table: torch.Tensor, r_in: torch.Tensor, B: int, grid, heads: int, window,
+                        shift, full_window, alpha: float, work: torch.Tensor, r_out: torch.Tensor) -> torch.Tensor:
+    """One block step of attention rollout through Swin's shifted-window attention (vc_window_rollout_step): r_out[j]
+    = alpha * mean_h sum_{i in win(j)} r_in[i] P_h[i][j] + (1 - alpha) * r_in[j], P_h recomputed from the block's kept
+    qkv bf16 [>= B*T*H*W, >= 3*heads*32] (q pre-scaled; v is not read) and its bias table f32 [ntab, heads] of the full
+    window, with the shift-region mask.  window / shift: the effective ones (swin3d.window_and_shift).  r_in / r_out
+    f32 [B*T*H*W] (any shape of that many elements); work from window_rollout_work."""
+    _dev(qkv, table, r_in, work, r_out)
+    T, H, W = grid
+    wt, wh, ww = window
+    st, sh, sw = shift
+    ft, fh, fw = full_window
+    ntok = B * T * H * W
+    ntab = (2 * ft - 1) * (2 * fh - 1) * (2 * fw - 1)
+    _need(qkv.dtype == torch.bfloat16 and qkv.dim() == 2 and qkv.stride(1) == 1, "window_rollout_step: qkv bf16 rows")
+    _need(qkv.shape[1] >= 3 * heads * 32 and qkv.shape[0] >= ntok, "window_rollout_step: qkv rows / columns")
+    _need(table.dtype == torch.float32 and table.is_contiguous() and tuple(table.shape) == (ntab, heads),
+          "window_rollout_step table: f32 [ntab, heads]")
+    for t, nm in ((r_in, "r_in"), (r_out, "r_out")):
+        _need(t.dtype == torch.float32 and t.is_contiguous() and t.numel() == ntok,
+              f"window_rollout_step: {nm} f32 [B*T*H*W]")
+    _need(T % wt == 0 and H % wh == 0 and W % ww == 0, "window_rollout_step: grid must be whole windows")
+    _need(work.dtype == torch.float32 and work.is_contiguous() and work.numel() >= 3 * heads * ntok,
+          "window_rollout_step work: contiguous f32 [3*heads*B*T*H*W]")
+    _lib.call("vc_window_rollout_step", _p(qkv), qkv.stride(0), _p(table), _p(r_in), B, T, H, W, heads, 32, wt, wh, ww,
+              st, sh, sw, ft, fh, fw, float(alpha), _p(work), work.numel(), _p(r_out), _stream(qkv))
+    return r_out
+
+
+def merge_rollout_spread(r_parent: torch.Tensor, B: int, grid, r_child: torch.Tensor) -> torch.Tensor:
+    """The rollout's hop through PatchMerging (vc_merge_rollout_spread): r_parent f32 [B*T*ceil(H/2)*ceil(W/2)] ->
+    r_child f32 [B*T*H*W] on the child `grid` (T, H, W), every merged token's relevance shared equally among its
+    existing children."""
+    _dev(r_parent, r_child)
+    T, H, W = grid
+    _need(r_parent.dtype == torch.float32 and r_parent.is_contiguous() and
+          r_parent.numel() == B * T * ((H + 1) // 2) * ((W + 1) // 2), "merge_rollout_spread: r_parent f32 [B*T*H2*W2]")
+    _need(r_child.dtype == torch.float32 and r_child.is_contiguous() and r_child.numel() == B * T * H * W,
+          "merge_rollout_spread: r_child f32 [B*T*H*W]")
+    _lib.call("vc_merge_rollout_spread", _p(r_parent), B, T, H, W, _p(r_child), _stream(r_parent))
+    return r_child
+
+
 def attention_bwd(qkv: torch.Tensor, out: torch.Tensor, dout: torch.Tensor, lse: torch.Tensor, delta: torch.Tensor,
                   B: int, S: int, H: int, dqkv: torch.Tensor, stream2: torch.cuda.Stream | None = None) -> torch.Tensor:
     """dqkv (q part = dL/dq' of the stored pre-scaled q', then dk, dv) of the joint attention.

@@ -189,6 +189,7 @@ class Swin3d(torch.nn.Module):
         # replayed (streams.GraphReplay); bit-identical logits
         self.graph_replay = False
         self._graphs = None
+        self._explain_ws = {}  # explain()'s own buffers per (B, geometry, device): not in _ws, which captured graphs hold on to
         self.stochastic_depth = True  # train step: torchvision's StochasticDepth on the residual branches
 
     def state_dict(self, *a, **k):
@@ -454,7 +455,9 @@ class Swin3d(torch.nn.Module):
                 window, _ = window_and_shift((t, h, w), c["window_size"], shift_full)
                 self._biasT(s, i, window, video.device)
 
-    def _forward_part(self, video: torch.Tensor, part: int, out=None) -> torch.Tensor:
+    def _forward_part(self, video: torch.Tensor, part: int, out=None, keep=None) -> torch.Tensor:
+        """keep (explain only): {"QKV": [per stage: bf16 [depth, M, roundup(3C, 128)]]} -- block i of stage s writes its
+        q|k|v to keep["QKV"][s][i] instead of the stage's shared buffer."""
         c = self.cfg
         B, Cin, T, H, W = video.shape
         pk = self._pack(video.device)
@@ -485,6 +488,8 @@ class Swin3d(torch.nn.Module):
                 shift_full = [0 if i % 2 == 0 else k // 2 for k in c["window_size"]]
                 window, shift = window_and_shift((t, h, w), c["window_size"], shift_full)
                 biasT = self._biasT(s, i, window, video.device)
+                if keep is not None:
+                    QKV = keep["QKV"][s][i]
                 tm("layernorm_grp_kernel", f"layernorm.s{s}", ntok * C * 6, "byte", ops.layernorm, X, blk["ln1"][0],
                    blk["ln1"][1], eps, Y, m=ntok)
                 ops.gemm(Y, blk["w_qkv"], blk["b_qkv"], "bias", QKV, flop=2.0 * ntok * 3 * C * C, op=f"qkv.s{s}",
@@ -522,6 +527,101 @@ class Swin3d(torch.nn.Module):
         t, h, w = grids[-1]
         return ops.pool_head(ws["stages"][-1]["X"], B, t * h * w, pk["norm"][0], pk["norm"][1], eps, pk["w_head"],
                              pk["b_head"], out=ws["logits"] if out is None else out, work=ws["pool_work"])
+
+
+    # ---- explain ------------------------------------------------------------------
+    EXPLAIN_METHODS = ("rollout",)
+
+    def _block_windows(self, grids):
+        """[stage][block] -> (window, shift), the effective ones of window_and_shift"""
+        c = self.cfg
+        return [[window_and_shift(g, c["window_size"], [0 if i % 2 == 0 else k // 2 for k in c["window_size"]])
+                 for i in range(c["depths"][s])] for s, g in enumerate(grids)]
+
+    def _explain_buffers(self, B, grids, device):
+        key = (B, tuple(grids), str(device))
+        if key not in self._explain_ws:
+            if len(self._explain_ws) >= 2:
+                self._explain_ws = {}
+            c = self.cfg
+            f = lambda n: torch.zeros(n, dtype=torch.float32, device=device)  # noqa: E731
+            qkv, r, work = [], [], []
+            for s, (t, h, w) in enumerate(grids):
+                C = c["embed_dim"] * 2 ** s
+                n = B * t * h * w
+                qkv.append(torch.zeros(c["depths"][s], _ru(n, 256), _ru(3 * C, 128), dtype=torch.bfloat16, device=device))
+                r.append((f(n), f(n)))
+                work.append(ops.window_rollout_work(B, (t, h, w), c["num_heads"][s], device))
+            t, h, w = grids[-1]
+            # the head is W . mean_n LN(x_n): the uniform row over the last stage's tokens, made on the host
+            seed = torch.full((B * t * h * w,), 1.0 / (t * h * w), dtype=torch.float32).to(device)
+            self._explain_ws[key] = dict(QKV=qkv, r=r, work=work, seed=seed,
+                                         logits=torch.zeros((B, self.num_classes), dtype=torch.float32, device=device))
+        return self._explain_ws[key]
+
+    @torch.no_grad()
+    def explain(self, video: torch.Tensor, method: str = "rollout", residual: float = 0.5):
+        """The logits and which part of the clip produced them: attention rollout (Abnar & Zuidema 2020) through
+        the shifted-window attention of every block.  Returns vivit.Explanation: `logits` f32 [B, classes] on the
+        device; on the host `token_relevance` f32 [B, N_0] over stage 0's tokens in the model's row order
+        ((t*H + h)*W + w) -- Swin has no CLS token, so there is NO CLS column, unlike ViViT's and TimeSformer's --
+        `saliency` f32 [B, T/pt, H/ph, W/pw] (the relevance divided by its per-clip sum) and `temporal` f32
+        [B, T/pt] (saliency summed over space); `target` is None (the map is not class-specific).
+
+        The head reads the mean of the last stage's tokens, so the rollout starts from the uniform row 1/N over
+        them and walks back, with a = `residual`: per block (last first) r <- r (a * mean_h(A) + (1 - a) I), A the
+        block's window attention with its relative-position bias and shift mask, block-diagonal over the shifted
+        windows (ops.window_rollout_step: the probabilities are recomputed from the kept q|k rows, never stored);
+        after the first block of a stage, every merged token shares its relevance equally among its existing
+        PatchMerging children (ops.merge_rollout_spread).  The MLP and the norms mix no tokens.  Every step matrix
+        has row sums 1, so the relevance keeps its sum 1.
+
+        Runs the ordinary eager forward (no graph replay, no stream split) and keeps every block's q|k|v in
+        buffers of its own, cached per (B, geometry, device): 165 MB at Swin-T 32 x 224^2, B = 1.  The forward's
+        workspaces, graphs, bias cache, packed weights and logits buffer are untouched.  The stage-0 relevance is
+        copied to the host once; normalisation and the sums happen there.  Refuses (no fallback): training mode,
+        CPU tensors, an unknown method, residual outside (0, 1], a video that is not [B, 3, T, H, W] with T/H/W
+        multiples of the patch size, stage grids that are not whole windows (which the window attention refuses)."""
+        from .vivit import Explanation
+        c = self.cfg
+        if method not in self.EXPLAIN_METHODS:
+            raise ValueError(f"explain: method must be one of {self.EXPLAIN_METHODS}, not {method!r}")
+        if not 0.0 < float(residual) <= 1.0:
+            raise ValueError(f"explain: residual must be in (0, 1], not {residual}")
+        if self.training:
+            raise RuntimeError("explain: inference only; call model.eval() first")
+        if video is None or video.device.type != "cuda":
+            raise RuntimeError("explain runs on the GPU only: move the clip batch to cuda")
+        if video.dim() != 5 or video.shape[1] != 3:
+            raise ValueError(f"video {tuple(video.shape)} must be [B, 3, T, H, W]")
+        B, _, T, H, W = video.shape
+        grids = self.geometry(B, T, H, W)  # ValueError unless T/H/W are multiples of the patch size
+        wins = self._block_windows(grids)
+        for s, g in enumerate(grids):
+            for window, _ in wins[s]:
+                if any(n % k for n, k in zip(g, window)):
+                    raise ValueError(f"explain: stage {s}'s token grid {g} is not whole windows of {tuple(window)}")
+        x = video.contiguous().float() if video.dtype != torch.float32 else video.contiguous()
+        buf = self._explain_buffers(B, grids, x.device)
+        logits = self._forward_part(x, 0, out=buf["logits"], keep=buf).clone()
+        pk = self._packed
+        alpha, full = float(residual), tuple(c["window_size"])
+        r_in = buf["seed"]
+        for s in reversed(range(len(grids))):
+            blocks = pk["stages"][s]["blocks"]
+            for i in reversed(range(len(blocks))):
+                window, shift = wins[s][i]
+                r_out = buf["r"][s][1] if r_in is buf["r"][s][0] else buf["r"][s][0]
+                ops.window_rollout_step(buf["QKV"][s][i], blocks[i]["table"], r_in, B, grids[s], c["num_heads"][s], window,
+                                        shift, full, alpha, buf["work"][s], r_out)
+                r_in = r_out
+            if s > 0:
+                r_in = ops.merge_rollout_spread(r_in, B, grids[s - 1], buf["r"][s - 1][0])
+        t0, h0, w0 = grids[0]
+        rel = r_in.cpu().reshape(B, t0 * h0 * w0)  # the one copy; the rest is host bookkeeping
+        rd = rel.double()
+        sal = (rd / rd.sum(dim=1, keepdim=True)).float().reshape(B, t0, h0, w0).contiguous()
+        return Explanation(logits, rel, sal, sal.sum(dim=(2, 3)), method)
 
 
 def create_model(logger=None, model_size="tiny", pretrained=True, num_classes=2, device="cuda", weights_seed: int = 0):

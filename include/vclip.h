@@ -617,6 +617,41 @@ int vc_temporal_rollout_step(const uint16_t* qkv, int64_t ld, const float* r_fra
                              float* r_frame_out, hipStream_t stream);
 
 /*
+ * One block step of attention rollout through Video Swin's shifted-window attention
+ * (csrc/window_rollout.hip).  Swin has no CLS token; its head reads the mean of the last stage's tokens,
+ * so the rollout carries a relevance over ALL tokens of a stage (seeded uniform) back through the blocks.
+ * qkv: the block's kept q'|k|v rows (bf16, token layout [B][T][H][W], q' = q * d^-1/2 * log2 e, head h of
+ * q' at columns 32h and of k at heads*32 + 32h; v is not read); table: the block's
+ * relative_position_bias_table, f32 [(2 full_t - 1)(2 full_h - 1)(2 full_w - 1), heads]; r_in, r_out f32
+ * [B*T*H*W].  (wt, wh, ww) / (st, sh, sw): the effective window and shift (clamped to the grid, as
+ * vc_window_attention3d takes them); (full_t, full_h, full_w): the model's window_size, on which the
+ * relative-position index is defined.  For every token j, win(j) its window after the roll by -shift:
+ *     r_out[j] = alpha * (1/heads) sum_h sum_{i in win(j)} r_in[i] * P_h[i][j] + (1 - alpha) * r_in[j]
+ *     P_h[i][.] = softmax2 over win(i) of q'_i . k_j + log2 e * table[idx(i, j)][h],
+ * pairs of different shift regions excluded (torchvision's -100).  The probabilities are recomputed with
+ * the exact row maximum and sum (no lse input) and never stored; the q'.k products are bf16 MFMA with
+ * fp32 accumulation, P and the sums fp32.  Every row of the step matrix sums to 1: sum r is conserved.
+ * work: caller scratch, work_elems >= 3*heads*B*T*H*W floats (per head and token the row maximum and
+ * r_in / row sum between the two passes over the scores, and the per-head partials, summed in head order
+ * by a third launch).  No atomics: deterministic, and clip b's result does not depend on B.  No qkv row past
+ * B*T*H*W and no padded window slot (volume -> multiple of 64) reaches a result.  head_dim 32, whole
+ * windows, window volume <= 448; r_out may not alias r_in, work may alias neither.
+ */
+int vc_window_rollout_step(const uint16_t* qkv, int64_t ld, const float* table, const float* r_in, int64_t B,
+                           int64_t T, int64_t H, int64_t W, int64_t heads, int64_t head_dim, int wt, int wh, int ww,
+                           int st, int sh, int sw, int full_t, int full_h, int full_w, float alpha, float* work,
+                           int64_t work_elems, float* r_out, hipStream_t stream);
+
+/*
+ * The rollout's hop through PatchMerging (csrc/window_rollout.hip): r_parent f32 [B*T*H2*W2] on the merged
+ * grid (H2 = (H+1)/2, W2 = (W+1)/2) -> r_child f32 [B*T*H*W]; merged token (t, i, j) gives an equal share
+ * of its relevance to each of its children (t, 2i + di, 2j + dj), di, dj in {0, 1}, that exist (a child
+ * past an odd edge does not), so the sum is conserved.  r_child may not alias r_parent.
+ */
+int vc_merge_rollout_spread(const float* r_parent, int64_t B, int64_t T, int64_t H, int64_t W, float* r_child,
+                            hipStream_t stream);
+
+/*
  * Attention backward (autograd of eager_attention_forward, TF5/models/vivit/modeling_vivit.py:
  * 149-174).  qkv: the forward's q'|k|v rows (q' = q*scale*log2 e, q_prescaled); out: the forward
  * output O; dout: dL/dO (same layout as out); lse from vc_attention_fwd_lse; delta: caller

@@ -34,6 +34,12 @@ times TimesformerForVideoClassification.explain instead: TimeSformer-B, 8 x 224^
 forward_ms, explain_rollout_ms, explain_cls_attention_ms, rollout_steps_ms (the 3 launches per layer alone: the
 spatial step's two and the temporal step's one), temporal_steps_ms (the twelve ops.temporal_rollout_step calls
 alone), forward_after_ms, and the size of the kept q|k|v and lse buffers.
+
+  python tools/saliency_time.py --family swin [--out profiles/saliency_time_swin.json]
+
+times Swin3d.explain: Swin-T, 32 x 224^2, B = 1, the same medians: forward_ms (the plain eager forward), explain_rollout_ms,
+rollout_ms (the 12 ops.window_rollout_step calls and the 3 ops.merge_rollout_spread hops alone, on the q|k|v explain
+kept), forward_after_ms, and the size of the kept q|k|v.
 """
 from __future__ import annotations
 
@@ -127,20 +133,82 @@ def timesformer(a) -> dict:
             "device": torch.cuda.get_device_name(0), "batches": {str(B): r}}
 
 
+def swin(a) -> dict:
+    """Swin-T, 32 x 224^2, B = 1: the plain eager forward, explain("rollout"), and the rollout alone (the 12 block
+    steps, three launches each, and the 3 PatchMerging hops) on the q|k|v explain kept"""
+    from vclip_amd import ops
+    from vclip_amd.build import source_hash
+    from vclip_amd.swin3d import create_model
+    from vclip_amd.weights import make_synthetic_video
+
+    model = create_model(None, "tiny", num_classes=2, device=DEV).eval()
+    c = model.cfg
+    B = 1
+    video = torch.from_numpy(make_synthetic_video(B, 32, 224, seed=1)).to(DEV)
+    grids = model.geometry(B, 32, 224, 224)
+    wins = model._block_windows(grids)
+    full = tuple(c["window_size"])
+
+    def forward():
+        model.forward_logits(video)
+
+    def explain():
+        model.explain(video, method="rollout")
+
+    r = {"grids": [list(g) for g in grids], "forward_ms": _median(forward, a.reps, a.warmup),
+         "explain_rollout_ms": _median(explain, a.reps, a.warmup)}
+    buf = model._explain_buffers(B, grids, video.device)  # as the last explain left them
+    pk = model._packed
+
+    def steps():
+        r_in = buf["seed"]
+        for s in reversed(range(len(grids))):
+            blocks = pk["stages"][s]["blocks"]
+            for i in reversed(range(len(blocks))):
+                window, shift = wins[s][i]
+                r_out = buf["r"][s][1] if r_in is buf["r"][s][0] else buf["r"][s][0]
+                ops.window_rollout_step(buf["QKV"][s][i], blocks[i]["table"], r_in, B, grids[s], c["num_heads"][s],
+                                        window, shift, full, 0.5, buf["work"][s], r_out)
+                r_in = r_out
+            if s > 0:
+                r_in = ops.merge_rollout_spread(r_in, B, grids[s - 1], buf["r"][s - 1][0])
+
+    r["rollout_ms"] = _median(steps, a.reps, a.warmup)
+    r["forward_after_ms"] = _median(forward, a.reps, a.warmup)
+    nsteps = sum(c["depths"])
+    r["rollout_launches"] = 3 * nsteps + len(grids) - 1
+    r["kept_qkv_bytes"] = sum(q.numel() * 2 for q in buf["QKV"])
+    # per block and pass 2 * 32 flop per (token, key of its window, head); two passes (normaliser, then the column sums)
+    flop = 0.0
+    for s, (t, h, w) in enumerate(grids):
+        for window, _ in wins[s]:
+            flop += 2 * 2.0 * 32 * B * t * h * w * window[0] * window[1] * window[2] * c["num_heads"][s]
+    r["rollout_flop"] = flop
+    r["rollout_tflops"] = flop / (r["rollout_ms"] * 1e-3) / 1e12
+    r["rollout_over_forward"] = r["rollout_ms"] / r["forward_ms"]
+    r["explain_over_forward"] = r["explain_rollout_ms"] / r["forward_ms"]
+    print(f"Swin-T B = {B}: forward {r['forward_ms']:.3f} ms (after {r['forward_after_ms']:.3f}), explain(rollout) "
+          f"{r['explain_rollout_ms']:.3f} ms, the rollout alone ({nsteps} steps + {len(grids) - 1} hops, "
+          f"{r['rollout_launches']} launches) {r['rollout_ms']:.3f} ms ({r['rollout_tflops']:.1f} TFLOP/s); "
+          f"kept q|k|v {r['kept_qkv_bytes'] / 1e6:.0f} MB", flush=True)
+    return {"model": "Swin-T 32 x 224^2", "reps": a.reps, "warmup": a.warmup, "build": source_hash(),
+            "device": torch.cuda.get_device_name(0), "batches": {str(B): r}}
+
+
 def main() -> int:
     ap = argparse.ArgumentParser()
-    ap.add_argument("--family", choices=("vivit", "timesformer"), default="vivit")
+    ap.add_argument("--family", choices=("vivit", "timesformer", "swin"), default="vivit")
     ap.add_argument("--out", default=None)
     ap.add_argument("--reps", type=int, default=15)
     ap.add_argument("--warmup", type=int, default=3)
     a = ap.parse_args()
     if a.out is None:
         a.out = os.path.join(ROOT, "profiles", "saliency_time.json" if a.family == "vivit" else
-                             "saliency_time_timesformer.json")
+                             f"saliency_time_{a.family}.json")
     if not torch.cuda.is_available():
         raise SystemExit("saliency_time.py needs a GPU")
-    if a.family == "timesformer":
-        res = timesformer(a)
+    if a.family in ("timesformer", "swin"):
+        res = timesformer(a) if a.family == "timesformer" else swin(a)
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:
             json.dump(res, f, indent=1)
