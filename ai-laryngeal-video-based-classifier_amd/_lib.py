@@ -82,6 +82,11 @@ SIGNATURES = {
     "vc_maxpool3d": ([c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_p, c_p, c_p, c_p, c_i64, c_p], c_int),
     "vc_avgpool_head": ([c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_p, c_p, c_p, c_i64, c_p, c_p, c_p], c_int),
     "vc_col2im_cl": ([c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_p, c_p, c_p, c_p, c_i64, c_p], c_int),
+    # ResNet3D saliency (csrc/cam.hip)
+    "vc_cam_seed": ([c_p, c_i64, c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_p, c_p, c_i64, c_p], c_int),
+    "vc_relu_bwd": ([c_p, c_i64, c_p, c_int, c_i64, c_p, c_int, c_i64, c_i64, c_i64, c_p, c_i64, c_p], c_int),
+    "vc_cam_weights": ([c_p, c_i64, c_i64, c_i64, c_i64, c_p, c_i64, c_p, c_p], c_int),
+    "vc_cam_map": ([c_int, c_p, c_i64, c_p, c_i64, c_p, c_i64, c_i64, c_i64, c_p, c_p], c_int),
     "vc_maxpool3d_bwd": ([c_p, c_i64, c_p, c_int, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_p, c_p, c_p, c_p, c_i64,
                           c_p], c_int),
     "vc_batchnorm_train_fwd": ([c_p, c_i64, c_i64, c_i64, c_p, c_p, c_f, c_f, c_p, c_p, c_p, c_int, c_i64, c_int, c_p,

@@ -237,6 +237,16 @@ SWIN_SALIENCY_HELP = (
     "with each time step's importance and the two source-frame indices it covers.")
 
 
+RESNET3D_SALIENCY_HELP = (
+    "absent (default): the label only, as the reference.  gradcam: Grad-CAM (Selvaraju et al. 2017); hirescam: HiResCAM "
+    "(Draelos & Carin 2020), the gradient times the activation per position (ResNet3d.explain), for --saliency_class at "
+    "--saliency_layer.  Writes <video>_saliency.npy (f32 [T, H/32, W/32] at res5, [T, H/16, W/16] at res4; the positive "
+    "part of the map, sums to 1, or all zero when the map has nothing positive) beside the result JSON, which gains a "
+    "\"saliency\" object with each frame's importance and its source-frame index.")
+# per family: the --saliency methods that take --saliency_class
+CLASS_SPECIFIC_SALIENCY = {"vivit": ("grad_rollout",), "resnet3d": ("gradcam", "hirescam")}
+
+
 def _temporal_patch(model) -> int:
     """sampled frames per time step of the family's saliency map: ViViT's tubelet depth, Swin's patch_size[0],
     1 for TimeSformer (per-frame patches)"""
@@ -250,8 +260,9 @@ def _temporal_patch(model) -> int:
 
 def build_parser(fam: Family, inference: bool, saliency: bool = False):
     """The folder's reference flags (plus ViViT's --saliency / --saliency_class).  saliency=True, as run_inference
-    builds it: the TimeSformer and Swin inference parsers also get their own --saliency; the two-argument form keeps
-    the flag surface those two families had before their `explain` existed."""
+    builds it: the TimeSformer, Swin and ResNet3D inference parsers also get their own --saliency (ResNet3D's with
+    --saliency_class and --saliency_layer); the two-argument form keeps the flag surface those families had before
+    their `explain` existed."""
     if fam.name == "lstm":
         return build_parser_lstm(inference)
     p = argparse.ArgumentParser(description=f"{fam.name} video classifier (libvclip, MI355X)")
@@ -282,6 +293,15 @@ def build_parser(fam: Family, inference: bool, saliency: bool = False):
                            help=TIMESFORMER_SALIENCY_HELP)
         elif fam.name == "swin" and saliency:
             p.add_argument("--saliency", type=str, default=None, choices=["rollout"], help=SWIN_SALIENCY_HELP)
+        elif fam.name == "resnet3d" and saliency:
+            p.add_argument("--saliency", type=str, default=None, choices=["gradcam", "hirescam"],
+                           help=RESNET3D_SALIENCY_HELP)
+            p.add_argument("--saliency_class", type=int, default=None,
+                           help="with --saliency: the class index whose evidence is mapped (absent: the predicted "
+                                "class); the result JSON's \"saliency\" object names it as target_class / target_label")
+            p.add_argument("--saliency_layer", type=str, default="res5", choices=["res5", "res4"],
+                           help="with --saliency: the stage whose output is explained (res4: twice the spatial "
+                                "resolution, through the res5 data-gradient chain)")
         return p
     required = fam.name in ("swin", "resnet3d")
     p.add_argument("--data_dir", type=str, required=True)
@@ -515,8 +535,9 @@ def run_inference(fam_name, argv=None):
     parser = build_parser(fam, inference=True, saliency=True)
     args = parser.parse_args(argv)
     saliency_class = getattr(args, "saliency_class", None)
-    if saliency_class is not None and args.saliency != "grad_rollout":
-        parser.error("--saliency_class needs --saliency grad_rollout")
+    class_methods = CLASS_SPECIFIC_SALIENCY.get(fam.name, ())
+    if saliency_class is not None and getattr(args, "saliency", None) not in class_methods:
+        parser.error(f"--saliency_class needs --saliency {' or '.join(class_methods)}")
     exp = ExperimentLogger(args.log_dir, prefix=f"{fam.prefix}-inference")
     logger = exp.get_logger()
     device = _device()
@@ -574,7 +595,10 @@ def run_inference(fam_name, argv=None):
     out.mkdir(parents=True, exist_ok=True)
     if saliency:
         # the label above is the ordinary forward's, the same with and without the flag; the map is explain's
-        if saliency == "grad_rollout":  # class-specific: the asked class, or the label printed above
+        if fam.name == "resnet3d":
+            ex = model.explain(x, method=saliency, target=pred if saliency_class is None else saliency_class,
+                               layer=args.saliency_layer)
+        elif saliency == "grad_rollout":  # class-specific: the asked class, or the label printed above
             ex = model.explain(x, method=saliency, target=pred if saliency_class is None else saliency_class)
         else:
             ex = model.explain(x, method=saliency)
@@ -587,6 +611,10 @@ def run_inference(fam_name, argv=None):
                            "tubelet_frame_indices": [frame_idx[i:i + kt] for i in range(0, len(frame_idx), kt)]}
         if ex.target is not None:
             res["saliency"].update(target_class=ex.target[0], target_label=id2label[ex.target[0]])
+        if fam.name == "resnet3d":
+            res["saliency"]["layer"] = args.saliency_layer
+            if not sal.any():  # the map has nothing positive: no evidence for the class at this layer
+                res["saliency"]["empty"] = True
         logger.info(f"Saliency ({saliency}): {out / npy}, most important tubelet {int(ex.temporal[0].argmax())}")
     with open(out / f"{Path(args.video_path).stem}_result.json", "w") as f:
         json.dump(res, f, indent=4)

@@ -390,9 +390,7 @@ class _Im2colCL(torch.autograd.Function):
         if da.stride(1) != 1:
             da = da.contiguous()
         dx = torch.empty(rows, C, dtype=torch.float32, device=da.device)
-        T, H, W = grid
-        _lib.call("vc_col2im_cl", _p(da), da.stride(0), B, T, H, W, C, ctypes.addressof(k := _i3(kernel)),
-                  ctypes.addressof(s_ := _i3(stride)), ctypes.addressof(p_ := _i3(pad)), _p(dx), C, _stream(da))
+        ops.col2im_cl(da, B, grid, C, kernel, stride, pad, dx)
         return dx, None, None, None, None, None, None
 
 

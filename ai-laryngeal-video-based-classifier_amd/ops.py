@@ -788,6 +788,111 @@ def avgpool_head(x: torch.Tensor, B: int, grid, C: int, pool_kernel, wc: torch.T
     return out
 
 
+# ---- ResNet3D saliency: Grad-CAM / HiResCAM (csrc/cam.hip) ------------------------------------
+
+CAM_MODE = {"gradcam": 0, "hirescam": 1}
+
+
+def _cl_rows(t: torch.Tensor, rows: int, C: int, what: str, dtypes=(torch.bfloat16,)):
+    """t: channels-last rows [>= rows, >= C] of one of `dtypes`, unit column stride, 16-B aligned rows"""
+    _need(t.dim() == 2 and t.dtype in dtypes and t.stride(1) == 1 and t.shape[0] >= rows and t.shape[1] >= C and
+          t.stride(0) % 8 == 0 and t.data_ptr() % 16 == 0, f"{what}: rows [>= {rows}, >= {C}], 16-B aligned, row stride % 8")
+
+
+def col2im_cl(da: torch.Tensor, B: int, grid, C: int, kernel, stride, pad, dx: torch.Tensor) -> torch.Tensor:
+    """The adjoint of conv3d_im2col on channels-last rows (vc_col2im_cl): da bf16 [>= B*To*Ho*Wo, >= kvol*C]
+    (columns (kt, kh, kw, c)) -> dx f32 [>= B*T*H*W, >= C] over the input grid (T, H, W); fixed gather order."""
+    import ctypes
+    _dev(da, dx)
+    T, H, W = grid
+    To, Ho, Wo = conv_out_size(grid, kernel, stride, pad)
+    kvol = kernel[0] * kernel[1] * kernel[2]
+    _need(all(0 <= p < k and s > 0 for k, s, p in zip(kernel, stride, pad)) and min(To, Ho, Wo) > 0, "col2im_cl geometry")
+    _need(da.dtype == torch.bfloat16 and da.dim() == 2 and da.stride(1) == 1 and da.shape[0] >= B * To * Ho * Wo and
+          da.shape[1] >= kvol * C, "col2im_cl da: bf16 [>= B*To*Ho*Wo, >= kvol*C]")
+    _need(dx.dtype == torch.float32 and dx.dim() == 2 and dx.stride(1) == 1 and dx.shape[0] >= B * T * H * W and
+          dx.shape[1] >= C, "col2im_cl dx: f32 [>= B*T*H*W, >= C]")
+    k, s, p = ((ctypes.c_int * 3)(*v) for v in (kernel, stride, pad))
+    _lib.call("vc_col2im_cl", _p(da), da.stride(0), B, T, H, W, C, ctypes.addressof(k), ctypes.addressof(s),
+              ctypes.addressof(p), _p(dx), dx.stride(0), _stream(da))
+    return dx
+
+
+def cam_seed(wc: torch.Tensor, target: torch.Tensor, B: int, grid, C: int, pool_kernel, out: torch.Tensor) -> torch.Tensor:
+    """d logit[target[b]] / d x of the head AvgPool3d(pool_kernel, stride 1) -> Linear(wc f32 [labels, C]) -> global
+    mean (vc_cam_seed): out bf16 rows [>= B*T*H*W, >= C], out[row, c] = cnt(t, h, w) / (npos * pt*ph*pw) *
+    wc[target[b], c].  target: int32 [B] on the device, every entry in [0, labels) (the caller's check)."""
+    import ctypes
+    _dev(wc, target, out)
+    T, H, W = grid
+    _need(wc.dtype == torch.float32 and wc.dim() == 2 and wc.is_contiguous() and wc.shape[1] == C and C % 8 == 0,
+          "cam_seed wc: contiguous f32 [labels, C], C % 8 == 0")
+    _need(target.dtype == torch.int32 and target.is_contiguous() and tuple(target.shape) == (B,), "cam_seed target: int32 [B]")
+    _need(all(0 < k <= n for k, n in zip(pool_kernel, grid)), "cam_seed: the pool must fit the grid")
+    _cl_rows(out, B * T * H * W, C, "cam_seed out")
+    pk = (ctypes.c_int * 3)(*pool_kernel)
+    _lib.call("vc_cam_seed", _p(wc), wc.shape[0], _p(target), B, T, H, W, C, ctypes.addressof(pk), _p(out), out.stride(0),
+              _stream(out))
+    return out
+
+
+def relu_bwd(y: torch.Tensor | None, d1: torch.Tensor, M: int, C: int, out: torch.Tensor,
+             d2: torch.Tensor | None = None) -> torch.Tensor:
+    """out[:M, :C] = (y is None or y > 0) ? d1 + (d2 or 0) : 0 as bf16 (vc_relu_bwd).  d1, d2: f32 or bf16 rows
+    [>= M, >= C]; y: bf16 activations.  A ReLU mask, the join of two gradients and the cast for the next GEMM."""
+    g16 = (torch.bfloat16, torch.float32)
+    ts = [t for t in (y, d1, d2, out) if t is not None]
+    _dev(*ts)
+    _need(C % 8 == 0 and M > 0, "relu_bwd: C % 8 == 0")
+    _cl_rows(d1, M, C, "relu_bwd d1", g16)
+    _cl_rows(out, M, C, "relu_bwd out")
+    if y is not None:
+        _cl_rows(y, M, C, "relu_bwd y")
+    if d2 is not None:
+        _cl_rows(d2, M, C, "relu_bwd d2", g16)
+    _lib.call("vc_relu_bwd", _p(y) if y is not None else None, y.stride(0) if y is not None else 0, _p(d1),
+              int(d1.dtype == torch.float32), d1.stride(0), _p(d2) if d2 is not None else None,
+              int(d2 is not None and d2.dtype == torch.float32), d2.stride(0) if d2 is not None else 0, M, C, _p(out),
+              out.stride(0), _stream(out))
+    return out
+
+
+def cam_weights_work(B: int, C: int, device) -> torch.Tensor:
+    """the f32 partial-sum buffer of cam_weights: 32 fixed-order partials per (clip, channel)"""
+    return torch.zeros(B * 32 * C, dtype=torch.float32, device=device)
+
+
+def cam_weights(g: torch.Tensor, B: int, N: int, C: int, work: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
+    """Grad-CAM's channel weights (vc_cam_weights): out f32 [B, C] = the mean over clip b's N rows of g bf16
+    [>= B*N, >= C]; work from cam_weights_work."""
+    _dev(g, work, out)
+    _need(C % 8 == 0, "cam_weights: C % 8 == 0")
+    _cl_rows(g, B * N, C, "cam_weights g")
+    _need(work.dtype == torch.float32 and work.is_contiguous() and work.numel() >= B * 32 * C,
+          "cam_weights work: contiguous f32 [B * 32 * C]")
+    _need(out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (B, C), "cam_weights out: f32 [B, C]")
+    _lib.call("vc_cam_weights", _p(g), g.stride(0), B, N, C, _p(work), work.numel(), _p(out), _stream(g))
+    return out
+
+
+def cam_map(mode: str, x: torch.Tensor, w: torch.Tensor, B: int, N: int, C: int, out: torch.Tensor) -> torch.Tensor:
+    """The signed class-activation map (vc_cam_map): out f32 [B*N]; x bf16 activations [>= B*N, >= C].  mode
+    "gradcam": out[row] = sum_c w[b, c] x[row, c] with w f32 [B, C] (cam_weights); "hirescam": sum_c w[row, c] x[row, c]
+    with w the bf16 gradient rows."""
+    _dev(x, w, out)
+    _need(mode in CAM_MODE, f"cam_map: mode must be one of {tuple(CAM_MODE)}")
+    _need(C % 8 == 0, "cam_map: C % 8 == 0")
+    _cl_rows(x, B * N, C, "cam_map x")
+    _need(out.dtype == torch.float32 and out.is_contiguous() and out.numel() == B * N, "cam_map out: f32 [B*N]")
+    if mode == "hirescam":
+        _cl_rows(w, B * N, C, "cam_map hirescam w")
+        _lib.call("vc_cam_map", 1, _p(x), x.stride(0), _p(w), w.stride(0), None, B, N, C, _p(out), _stream(x))
+    else:
+        _need(w.dtype == torch.float32 and w.is_contiguous() and tuple(w.shape) == (B, C), "cam_map gradcam w: f32 [B, C]")
+        _lib.call("vc_cam_map", 0, _p(x), x.stride(0), None, 0, _p(w), B, N, C, _p(out), _stream(x))
+    return out
+
+
 # ---- train step (SURVEY.md §8 a16) -----------------------------------------------------------
 
 def attention_fwd_lse(qkv: torch.Tensor, B: int, S: int, H: int, out: torch.Tensor, lse: torch.Tensor,

@@ -70,6 +70,7 @@ class ResNet3d(torch.nn.Module):
         # per-convolution overrides {"conv_a.s4": (ring, tile), ...} of vc_conv3d_gemm_bf16_cfg (tile 0 auto,
         # 1 = 64 x 128, 2 = 128 x 128; ring 0 auto, 2, 3, 4); bit-identical for any setting
         self.conv_cfg = {}
+        self._explain_ws = {}  # explain's kept activations and gradient buffers per (B, geometry, layer, device)
 
     def _conv_kw(self, op: str, s: int) -> dict:
         ring, tile = self.conv_cfg.get(op, (self.conv_ring.get(f"s{s + 2}", 0), 0))
@@ -343,19 +344,24 @@ class ResNet3d(torch.nn.Module):
         return run_split(self, video, ns, self._forward_part, self.cfg["num_classes"],
                          prepare=lambda: self._pack(video.device))
 
-    def _forward_part(self, video: torch.Tensor, part: int, out=None) -> torch.Tensor:
-        x, B, grid, C, ws = self.forward_features(video, part)
+    def _forward_part(self, video: torch.Tensor, part: int, out=None, keep=None) -> torch.Tensor:
+        """keep (explain only): forward_features' keep buffers; the head then pools in keep["head_work"]"""
+        x, B, grid, C, ws = self.forward_features(video, part, keep=keep)
         pk = self._packed
         c = self.cfg
         Tf, Hf, Wf = grid
         pt, ph, pw = c["head_pool"]
         npos = (Tf - pt + 1) * (Hf - ph + 1) * (Wf - pw + 1)
         return ops.timed("avgpool_head", "head", B * Tf * Hf * Wf * C * 2 + npos * B * C * 4, "byte", ops.avgpool_head,
-                         x, B, grid, C, c["head_pool"], pk["w_head"], pk["b_head"], ws["head_work"],
-                         ws["logits"] if out is None else out)
+                         x, B, grid, C, c["head_pool"], pk["w_head"], pk["b_head"],
+                         ws["head_work"] if keep is None else keep["head_work"], ws["logits"] if out is None else out)
 
-    def forward_features(self, video: torch.Tensor, part: int = 0):
-        """Stem + the four stages; returns (last activations [rows, C] bf16, B, (T, H, W), C, workspace)."""
+    def forward_features(self, video: torch.Tensor, part: int = 0, keep=None):
+        """Stem + the four stages; returns (last activations [rows, C] bf16, B, (T, H, W), C, workspace).
+        keep (explain only, _explain_buffers): {"stage": s, "x": bf16 rows, "blocks": {(stage, block): {"a", "b",
+        "out"}}} -- the last block of stage s writes its output to keep["x"] and every block of the later stages its
+        conv_a / conv_b activations and its output to buffers of its own instead of the stage's shared ones (the same
+        launches on other output pointers: bit-identical values)."""
         c = self.cfg
         B, C, T, H, W = video.shape
         if C != 3:
@@ -406,6 +412,8 @@ class ResNet3d(torch.nn.Module):
                 stride = (1, ss, ss) if i == 0 else (1, 1, 1)
                 gi = g_in if i == 0 else g
                 xin = x
+                kept = keep["blocks"].get((s, i)) if keep is not None else None
+                ya, yb = (kept["a"], kept["b"]) if kept is not None else (act["a"], act["b"])
                 # branch1: 1x1x1 conv (+ stride) + BN, or the identity
                 if "b1" in blk:
                     fl = 2.0 * vol(g) * dout * cin
@@ -427,38 +435,285 @@ class ResNet3d(torch.nn.Module):
                 if tuple(ka) == (1, 1, 1) and self.implicit_conv and inner % 128 and inner % 64 == 0 and cin % 64 == 0:
                     # 64 output channels: the 256 x 64 implicit-GEMM tile (no MFMAs on the zero-padded channels)
                     ops.conv3d_gemm(xin, B, gi, cin, ka, (1, 1, 1), (0, 0, 0), blk["a"][0], blk["a"][1], "bias_relu",
-                                    act["a"], flop=fl, op=f"conv_a.s{s + 2}", n=inner, **self._conv_kw(f"conv_a.s{s + 2}", s))
+                                    ya, flop=fl, op=f"conv_a.s{s + 2}", n=inner, **self._conv_kw(f"conv_a.s{s + 2}", s))
                 elif tuple(ka) == (1, 1, 1):
-                    ops.gemm(xin, blk["a"][0], blk["a"][1], "bias_relu", act["a"], m=rows(gi), flop=fl, op=f"conv_a.s{s + 2}")
+                    ops.gemm(xin, blk["a"][0], blk["a"][1], "bias_relu", ya, m=rows(gi), flop=fl, op=f"conv_a.s{s + 2}")
                 elif self.implicit_conv and cin % 64 == 0:
                     ops.conv3d_gemm(xin, B, gi, cin, ka, (1, 1, 1), tuple(k // 2 for k in ka), blk["a"][0], blk["a"][1],
-                                    "bias_relu", act["a"], flop=fl, op=f"conv_a.s{s + 2}", n=_ru(inner, 64),
+                                    "bias_relu", ya, flop=fl, op=f"conv_a.s{s + 2}", n=_ru(inner, 64),
                                     **self._conv_kw(f"conv_a.s{s + 2}", s))
                 else:
                     A = col(rows(gi), ka[0] * cin)
                     tm("conv3d_im2col_kernel", "im2col", vol(gi) * cin * 2 * (1 + ka[0]), "byte", ops.conv3d_im2col,
                        xin, "cl_bf16", B, gi, cin, ka, (1, 1, 1), tuple(k // 2 for k in ka), A)
-                    ops.gemm(A, blk["a"][0], blk["a"][1], "bias_relu", act["a"], flop=fl, op=f"conv_a.s{s + 2}")
+                    ops.gemm(A, blk["a"][0], blk["a"][1], "bias_relu", ya, flop=fl, op=f"conv_a.s{s + 2}")
                 # conv_b (1,3,3) with the stage stride (+ BN + ReLU)
                 if self.implicit_conv and inner % 64 == 0:
-                    ops.conv3d_gemm(act["a"], B, gi, inner, (1, 3, 3), stride, (0, 1, 1), blk["b"][0], blk["b"][1],
-                                    "bias_relu", act["b"], flop=2.0 * vol(g) * inner * inner * 9, op=f"conv_b.s{s + 2}",
+                    ops.conv3d_gemm(ya, B, gi, inner, (1, 3, 3), stride, (0, 1, 1), blk["b"][0], blk["b"][1],
+                                    "bias_relu", yb, flop=2.0 * vol(g) * inner * inner * 9, op=f"conv_b.s{s + 2}",
                                     n=_ru(inner, 64), **self._conv_kw(f"conv_b.s{s + 2}", s))
                 else:
                     A = col(rows(g), 9 * inner)
                     tm("conv3d_im2col_kernel", "im2col", (vol(gi) + 9 * vol(g)) * inner * 2, "byte", ops.conv3d_im2col,
-                       act["a"], "cl_bf16", B, gi, inner, (1, 3, 3), stride, (0, 1, 1), A)
-                    ops.gemm(A, blk["b"][0], blk["b"][1], "bias_relu", act["b"], flop=2.0 * vol(g) * inner * inner * 9,
+                       ya, "cl_bf16", B, gi, inner, (1, 3, 3), stride, (0, 1, 1), A)
+                    ops.gemm(A, blk["b"][0], blk["b"][1], "bias_relu", yb, flop=2.0 * vol(g) * inner * inner * 9,
                              op=f"conv_b.s{s + 2}")
                 # conv_c 1x1x1 + BN + skip + ReLU
-                out = act["x"] if xin is not act["x"] else act["x2"]
+                if kept is not None:
+                    out = kept["out"]
+                elif keep is not None and s == keep["stage"] and i == len(st["blocks"]) - 1:
+                    out = keep["x"]
+                else:
+                    out = act["x"] if xin is not act["x"] else act["x2"]
                 # HBM-bound at every stage (K = inner = 64 .. 512 against a bf16 residual in and a bf16
                 # output: 28 .. 229 flop/B, below the 312 flop/B ridge): filed under its bytes
-                ops.gemm(act["b"][:, :inner], blk["c"][0], blk["c"][1], "bias_resid_relu", out, aux=skip,
+                ops.gemm(yb[:, :inner], blk["c"][0], blk["c"][1], "bias_resid_relu", out, aux=skip,
                          op=f"conv_c.s{s + 2}", nbytes=2.0 * (vol(g) * (inner + 2 * dout) + dout * inner))
                 x, cin = out, dout
             g_in = g
         return x, B, grids[-1], cin, ws
+
+
+    # ---- explain: Grad-CAM / HiResCAM ---------------------------------------------------
+    EXPLAIN_METHODS = ("gradcam", "hirescam")
+    EXPLAIN_LAYERS = ("res5", "res4")  # res2 / res3: out of scope
+
+    def _pack_transposed(self, pk, first_stage: int):
+        """pk["wt"][s][i]: the transposed folded bf16 weights {"b1", "a", "b", "c"} -> [roundup(K, 128), N] of the
+        blocks of stages >= first_stage, built on the first explain that needs them and cached with the packed
+        weights (same key).  BatchNorm is folded into the weight, so its transpose is the exact data-gradient
+        operand of the eval-mode convolution; rows past K are zero (the GEMM's output-column padding)."""
+        wt = pk.setdefault("wt", {})
+        for s in range(first_stage, len(pk["stages"])):
+            if s in wt:
+                continue
+            st = pk["stages"][s]
+            blocks = []
+            for blk in st["blocks"]:
+                t = {}
+                for name, cout in (("b1", st["dout"]), ("a", st["inner"]), ("b", st["inner"]), ("c", st["dout"])):
+                    if name not in blk:
+                        continue
+                    if cout % 64:
+                        raise NotImplementedError(f"explain: the data-gradient GEMMs need channel counts % 64 == 0, not {cout}")
+                    w = blk[name][0]
+                    m = torch.zeros((_ru(w.shape[1], 128), cout), dtype=torch.bfloat16, device=w.device)
+                    m[:w.shape[1]] = w[:cout].t()
+                    t[name] = m
+                blocks.append(t)
+            wt[s] = blocks
+        return wt
+
+    def _explain_buffers(self, B, T, H, W, layer, device):
+        """The kept activations (forward_features' keep) and the chain's gradient buffers, cached per (B, geometry,
+        layer, device).  Per block after the layer: its a / b / output, its masked output gradient `d`, and the two
+        gradients its input receives (dIn, and dsk when the skip is a convolution); the GEMM and col2im outputs
+        consumed at once are shared scratch, sized by the largest block."""
+        key = (B, T, H, W, layer, str(device))
+        if key in self._explain_ws:
+            return self._explain_ws[key]
+        if len(self._explain_ws) >= 2:
+            self._explain_ws = {}
+        c, pk = self.cfg, self._packed
+        n = len(c["depths"])
+        ls = n - 1 if layer == "res5" else n - 2
+        _, grids = self.geometry(T, H, W)
+        bf, f32 = torch.bfloat16, torch.float32
+        rows = lambda g: _ru(B * g[0] * g[1] * g[2], 256)  # noqa: E731
+        z = lambda r, cols, dt=bf: torch.zeros((r, cols), dtype=dt, device=device)  # noqa: E731
+        Cl, Cf = pk["stages"][ls]["dout"], pk["stages"][-1]["dout"]
+        gl, gf = grids[ls], grids[-1]
+        Nl = gl[0] * gl[1] * gl[2]
+        buf = dict(stage=ls, grid=gl, C=Cl, x=z(rows(gl), Cl), blocks={}, chain=[],
+                   head_work=torch.zeros(B * Cf * 33, dtype=f32, device=device),
+                   logits=torch.zeros((B, c["num_classes"]), dtype=f32, device=device),
+                   target=torch.zeros(B, dtype=torch.int32, device=device), seed=z(rows(gf), Cf),
+                   alpha=torch.zeros((B, Cl), dtype=f32, device=device), cam_work=ops.cam_weights_work(B, Cl, device),
+                   map=torch.zeros(B * Nl, dtype=f32, device=device))
+        big = {}
+
+        def scratch(name, r, cols):
+            big[name] = max(big.get(name, 0), r * cols)
+
+        for s in range(ls + 1, n):
+            st = pk["stages"][s]
+            g, inner, dout = grids[s], st["inner"], st["dout"]
+            ip = _ru(inner, 128)
+            ka = tuple(c["conv_a_kernels"][s])
+            kv = ka[0] * ka[1] * ka[2]
+            ss = c["spatial_strides"][s]
+            for i, blk in enumerate(st["blocks"]):
+                gi = grids[s - 1] if i == 0 else g
+                cin = st["din"] if i == 0 else dout
+                stride = (1, ss, ss) if i == 0 else (1, 1, 1)
+                buf["blocks"][(s, i)] = dict(a=z(rows(gi), ip), b=z(rows(g), ip), out=z(rows(g), dout))
+                ch = dict(s=s, i=i, g=g, gi=gi, cin=cin, inner=inner, dout=dout, stride=stride, ka=ka, d=z(rows(g), dout))
+                if "b1" in blk:
+                    if stride != (1, 1, 1):
+                        scratch("tsk", rows(g), _ru(cin, 128))
+                        ch["dsk"] = z(rows(gi), cin, f32)
+                    else:
+                        ch["dsk"] = z(rows(g), _ru(cin, 128))
+                if kv > 1:
+                    scratch("ta", rows(gi), _ru(kv * cin, 128))
+                    ch["dIn"] = z(rows(gi), cin, f32)
+                else:
+                    ch["dIn"] = z(rows(gi), _ru(cin, 128))
+                scratch("tc", rows(g), ip)
+                scratch("dB", rows(g), ip)
+                scratch("tb", rows(g), _ru(9 * inner, 128))
+                scratch("cb", rows(gi), inner)
+                scratch("dA", rows(gi), ip)
+                buf["chain"].append(ch)
+        buf["scratch"] = {k: torch.zeros(v, dtype=f32 if k == "cb" else bf, device=device) for k, v in big.items()}
+        if buf["chain"]:
+            buf["g"] = z(rows(gl), Cl)
+        buf["kept_bytes"] = buf["x"].numel() * 2 + sum(t.numel() * 2 for kb in buf["blocks"].values() for t in kb.values())
+        self._explain_ws[key] = buf
+        return buf
+
+    def _explain_chain(self, buf, B: int) -> torch.Tensor:
+        """The eval-mode data-gradient chain from buf["seed"] (the gradient at the last block's post-ReLU output) back
+        to the explained layer: bf16 [rows, C_layer], the gradient of the target logit with respect to that layer's
+        activations.  No weight gradient is formed.  Per block, last first, with dOut = (d1 [, d2]):
+
+            d   = relu_bwd(out, d1 [, d2])                          the output ReLU, joining the two gradients
+            dsk = d | col2im_(1,1,1),stride(gemm(d, W1^T))          identity skip | branch1
+            dB  = relu_bwd(b, gemm(d, Wc^T))
+            dA  = relu_bwd(a, col2im_(1,3,3),stride(gemm(dB, Wb^T)))
+            dIn = col2im_(kt,1,1)(gemm(dA, Wa^T))                   the GEMM output itself when kt = 1
+
+        and (dIn, dsk) is the next block's dOut; at the layer they are joined unmasked (relu_bwd with y = None)."""
+        from .autograd_ops import _zeros_f32
+        if not buf["chain"]:
+            return buf["seed"]
+        wt = self._packed["wt"]
+        dev = buf["seed"].device
+        tm = ops.timed
+        rows = lambda g: _ru(B * g[0] * g[1] * g[2], 256)  # noqa: E731
+        vol = lambda g: B * g[0] * g[1] * g[2]  # noqa: E731
+        view = lambda name, r, cols: buf["scratch"][name][: r * cols].view(r, cols)  # noqa: E731
+        esz = lambda t: t.element_size()  # noqa: E731
+
+        def relu(y, d1, M, C, out, d2=None):
+            nb = M * C * (2 + esz(d1) + (2 if y is not None else 0) + (esz(d2) if d2 is not None else 0))
+            return tm("relu_bwd_kernel", "cam.relu_bwd", nb, "byte", ops.relu_bwd, y, d1, M, C, out, d2)
+
+        def dgrad(d, w, out, op):
+            return ops.gemm(d, w, _zeros_f32(w.shape[0], dev), "bias", out, op=op)
+
+        def col2im(da, grid, C, kernel, stride, pad, dx):
+            kv = kernel[0] * kernel[1] * kernel[2]
+            To, Ho, Wo = ops.conv_out_size(grid, kernel, stride, pad)
+            return tm("col2im_cl_kernel", "cam.col2im", B * To * Ho * Wo * kv * C * 2 + vol(grid) * C * 4, "byte",
+                      ops.col2im_cl, da, B, grid, C, kernel, stride, pad, dx)
+
+        d1, d2 = buf["seed"], None
+        for ch in reversed(buf["chain"]):
+            s, g, gi, cin, inner, dout = ch["s"], ch["g"], ch["gi"], ch["cin"], ch["inner"], ch["dout"]
+            kept, w = buf["blocks"][(s, ch["i"])], wt[s][ch["i"]]
+            ip = _ru(inner, 128)
+            d = relu(kept["out"], d1, vol(g), dout, ch["d"], d2)
+            if "b1" not in w:
+                dsk = d
+            elif ch["stride"] != (1, 1, 1):
+                tsk = dgrad(d, w["b1"], view("tsk", rows(g), _ru(cin, 128)), f"cam.dgrad.branch1.s{s + 2}")
+                dsk = col2im(tsk, gi, cin, (1, 1, 1), ch["stride"], (0, 0, 0), ch["dsk"])
+            else:
+                dsk = dgrad(d, w["b1"], ch["dsk"], f"cam.dgrad.branch1.s{s + 2}")
+            tc = dgrad(d, w["c"], view("tc", rows(g), ip), f"cam.dgrad.conv_c.s{s + 2}")
+            dB = relu(kept["b"], tc, vol(g), inner, view("dB", rows(g), ip))
+            tb = dgrad(dB[:, :inner], w["b"], view("tb", rows(g), _ru(9 * inner, 128)), f"cam.dgrad.conv_b.s{s + 2}")
+            cb = col2im(tb, gi, inner, (1, 3, 3), ch["stride"], (0, 1, 1), view("cb", rows(gi), inner))
+            dA = relu(kept["a"], cb, vol(gi), inner, view("dA", rows(gi), ip))
+            ka = ch["ka"]
+            kv = ka[0] * ka[1] * ka[2]
+            if kv > 1:
+                ta = dgrad(dA[:, :inner], w["a"], view("ta", rows(gi), _ru(kv * cin, 128)), f"cam.dgrad.conv_a.s{s + 2}")
+                dIn = col2im(ta, gi, cin, ka, (1, 1, 1), tuple(k // 2 for k in ka), ch["dIn"])
+            else:
+                dIn = dgrad(dA[:, :inner], w["a"], ch["dIn"], f"cam.dgrad.conv_a.s{s + 2}")
+            d1, d2 = dIn, dsk
+        return relu(None, d1, vol(buf["grid"]), buf["C"], buf["g"], d2)
+
+    @torch.no_grad()
+    def explain(self, video: torch.Tensor, method: str = "gradcam", target=None, layer: str = "res5"):
+        """The logits and which part of the clip produced logit `target`: Grad-CAM (Selvaraju et al. 2017) or HiResCAM
+        (Draelos & Carin 2020) on the output of `layer` ("res5": T x H/32 x W/32, or "res4": T x H/16 x W/16).
+        With A the layer's activations and G = d logit[target] / d A:
+
+            "gradcam"   map[t, h, w] = sum_c mean_{t,h,w}(G)[c] * A[c, t, h, w]
+            "hirescam"  map[t, h, w] = sum_c G[c, t, h, w] * A[c, t, h, w]
+
+        G starts at the head in closed form (ops.cam_seed: AvgPool3d(stride 1) -> Linear -> global mean weights a
+        position by the pool windows that cover it) and, for "res4", walks back through the res5 bottlenecks with
+        their BatchNorms folded (_explain_chain: data-gradient GEMMs on the transposed folded weights, col2im, ReLU
+        masks; no weight gradients).  At "res5" HiResCAM sums to logit - bias, and Grad-CAM on this linear head is
+        classic CAM.  `target`: None (each clip's argmax), an int, or a sequence / tensor of B ints.
+
+        Returns vivit.Explanation: `logits` f32 [B, classes] on the device (a clone); on the host `token_relevance`
+        f32 [B, T*H_l*W_l], the SIGNED map in the row order (t*H_l + h)*W_l + w (the one copy), `saliency` f32
+        [B, T, H_l, W_l] = relu(map) divided by its per-clip sum, `temporal` f32 [B, T] (saliency summed over space),
+        `method`, and `target`, the B class indices.  A clip whose map has nothing positive -- no evidence FOR the
+        class at that layer, common for the class the clip was not assigned to -- gets an all-zero `saliency` and
+        `temporal`; `token_relevance` still holds its (non-positive) map.
+
+        Runs the ordinary eager forward (one stream, no graph replay) with the activations after the layer kept in
+        buffers of its own, cached per (B, geometry, layer, device); the forward's workspaces, packed weights, graphs
+        and logits buffer are untouched.  Refuses (no fallback): training mode, CPU tensors, an unknown method or
+        layer ("res2" / "res3" are not supported), a bad target, a video that is not [B, 3, T, H, W], a head pool
+        that does not fit the final grid."""
+        from .vivit import Explanation, VivitForVideoClassification
+        c = self.cfg
+        if method not in self.EXPLAIN_METHODS:
+            raise ValueError(f"explain: method must be one of {self.EXPLAIN_METHODS}, not {method!r}")
+        if layer not in self.EXPLAIN_LAYERS:
+            raise ValueError(f"explain: layer must be one of {self.EXPLAIN_LAYERS}, not {layer!r}")
+        if self.training:
+            raise RuntimeError("explain: inference only; call model.eval() first")
+        if not isinstance(video, torch.Tensor) or video.device.type != "cuda":
+            raise RuntimeError("explain runs on the GPU only: move the clip batch to cuda")
+        if video.dim() != 5 or video.shape[1] != 3:
+            raise ValueError(f"video {tuple(video.shape)} must be [B, 3, T, H, W]")
+        B, _, T, H, W = video.shape
+        target, scalar = VivitForVideoClassification._check_targets(target, c["num_classes"])
+        if target is not None:
+            target = target * B if scalar else target
+            if len(target) != B:
+                raise ValueError(f"explain: target has {len(target)} entries for {B} clips")
+        _, grids = self.geometry(T, H, W)
+        gf = grids[-1]
+        if any(k <= 0 or k > n for k, n in zip(c["head_pool"], gf)):
+            raise ValueError(f"explain: the head pool {tuple(c['head_pool'])} does not fit the final grid {tuple(gf)}")
+        x = video.contiguous().float() if video.dtype != torch.float32 else video.contiguous()
+        pk = self._pack(x.device)
+        if "w_head" not in pk:
+            raise RuntimeError("explain: the model has no classification head (blocks.5.proj)")
+        buf = self._explain_buffers(B, T, H, W, layer, x.device)
+        self._pack_transposed(pk, buf["stage"] + 1)
+        logits = self._forward_part(x, 0, out=buf["logits"], keep=buf).clone()
+        if target is None:
+            target = logits.argmax(dim=1).tolist()
+        buf["target"].copy_(torch.tensor(target, dtype=torch.int32))
+        Cf, (Tl, Hl, Wl), Cl = buf["seed"].shape[1], buf["grid"], buf["C"]
+        Nl, Nf = Tl * Hl * Wl, gf[0] * gf[1] * gf[2]
+        tm = ops.timed
+        tm("cam_seed_kernel", "cam.seed", B * Nf * Cf * 2, "byte", ops.cam_seed, pk["w_head"], buf["target"], B, gf, Cf,
+           c["head_pool"], buf["seed"])
+        G = self._explain_chain(buf, B)
+        if method == "gradcam":
+            tm("cam_weights_kernels", "cam.weights", B * Nl * Cl * 2, "byte", ops.cam_weights, G, B, Nl, Cl, buf["cam_work"],
+               buf["alpha"])
+            tm("cam_map_kernel<false>", "cam.map", B * Nl * Cl * 2, "byte", ops.cam_map, "gradcam", buf["x"], buf["alpha"],
+               B, Nl, Cl, buf["map"])
+        else:
+            tm("cam_map_kernel<true>", "cam.map", B * Nl * Cl * 4, "byte", ops.cam_map, "hirescam", buf["x"], G, B, Nl, Cl,
+               buf["map"])
+        rel = buf["map"].cpu().reshape(B, Nl)  # the one copy; the rest is host bookkeeping
+        pos = rel.double().clamp_min(0)
+        tot = pos.sum(dim=1, keepdim=True)
+        sal = torch.where(tot > 0, pos / tot.clamp_min(1e-300), torch.zeros_like(pos)).float().reshape(B, Tl, Hl, Wl)
+        return Explanation(logits, rel, sal.contiguous(), sal.sum(dim=(2, 3)), method, target=target)
 
 
 def create_model(logger=None, device="cuda", weights_seed: int = 0):

@@ -81,7 +81,8 @@ class Explanation:
     """What VivitForVideoClassification.explain returns: `logits` f32 [B, labels] on the device;
     `token_relevance` f32 [B, S] (column 0 is CLS), `saliency` f32 [B, T/kt, H/kh, W/kw] (the patch tokens'
     relevance divided by its per-clip sum) and `temporal` f32 [B, T/kt] (saliency summed over space) on the host.
-    `target`: the B class indices a class-specific method ("grad_rollout") explained, None for the others."""
+    `target`: the B class indices a class-specific method ("grad_rollout"; ResNet3d.explain's Grad-CAM / HiResCAM, whose
+    `token_relevance` is the signed map with no CLS column) explained, None for the others."""
 
     def __init__(self, logits, token_relevance, saliency, temporal, method, target=None):
         self.logits, self.token_relevance, self.saliency, self.temporal = logits, token_relevance, saliency, temporal
@@ -682,9 +683,13 @@ class VivitForVideoClassification(torch.nn.Module):
     def _explain_targets(self, target):
         """`target` of explain checked against the labels: (None or a list of class indices, whether it was one int
         for every clip)"""
+        return self._check_targets(target, self.config.num_labels)
+
+    @staticmethod
+    def _check_targets(target, nl: int):
+        """_explain_targets against `nl` labels (shared with ResNet3d.explain)"""
         if target is None:
             return None, False
-        nl = self.config.num_labels
         if isinstance(target, torch.Tensor):
             if target.is_floating_point() or target.dtype == torch.bool:
                 raise ValueError("explain: target must hold integers")

@@ -942,6 +942,36 @@ int vc_mlp_head_bwd(const float* h, const float* W1, const float* W2, const floa
                     const float* dlogits, int64_t B, int64_t hidden, int64_t H1, int64_t num_labels, float* dh, float* dW1,
                     float* db1, float* dW2, float* db2, hipStream_t stream);
 
+/* ---- ResNet3D saliency: Grad-CAM / HiResCAM (cam.hip; ResNet3d.explain) ----
+ * Rows are channels-last ((b*T + t)*H + h)*W + w with row stride ld >= C, C % 8 == 0, ld % 8 == 0, 16-B aligned.
+ * Only rows < B*T*H*W and columns < C are read or written.  No atomics: results are bit-reproducible and clip
+ * b's do not depend on B. */
+
+/* d logit[target[b]] / d x of the head AvgPool3d(pool_kernel, stride 1) -> Linear(Wc f32 [num_labels][C]) ->
+ * global mean, as bf16: g[row][c] = cnt(t, h, w) / (npos * pt*ph*pw) * Wc[target[b]][c]; cnt = the product over
+ * the axes of the pool windows covering the index, min(i, L - k) - max(0, i - k + 1) + 1; npos = the pooled
+ * positions.  target: int32 [B] on the device (a class outside [0, num_labels) writes zeros). */
+int vc_cam_seed(const float* Wc, int64_t num_labels, const int* target, int64_t B, int64_t T, int64_t H, int64_t W,
+                int64_t C, const int* pool_kernel, uint16_t* g, int64_t ldg, hipStream_t stream);
+
+/* out[row][c] = (y == NULL || y[row][c] > 0) ? d1[row][c] + (d2 ? d2[row][c] : 0) : 0 as bf16, M rows.  d1 / d2:
+ * f32 when d1_f32 / d2_f32, else bf16 (vc_col2im_cl writes f32, the GEMM bf16); y: bf16 activations.  The ReLU
+ * masks of the eval-mode data-gradient chain, the join of a block's skip and branch gradients, and the cast. */
+int vc_relu_bwd(const uint16_t* y, int64_t ldy, const void* d1, int d1_f32, int64_t ldd1, const void* d2, int d2_f32,
+                int64_t ldd2, int64_t M, int64_t C, uint16_t* out, int64_t ldo, hipStream_t stream);
+
+/* alpha f32 [B][C] = the mean over clip b's N rows of g (bf16).  work: caller scratch f32 [B * 32 * C]
+ * (fixed-order partial sums, as vc_avgpool_head's). */
+int vc_cam_weights(const uint16_t* g, int64_t ldg, int64_t B, int64_t N, int64_t C, float* work, int64_t work_elems,
+                   float* alpha, hipStream_t stream);
+
+#define VC_CAM_GRADCAM 0
+#define VC_CAM_HIRESCAM 1
+/* out f32 [B*N], signed (no ReLU): VC_CAM_GRADCAM sum_c alpha[b][c] x[row][c] (g unused);
+ * VC_CAM_HIRESCAM sum_c g[row][c] x[row][c] (alpha unused).  x, g bf16. */
+int vc_cam_map(int mode, const uint16_t* x, int64_t ldx, const uint16_t* g, int64_t ldg, const float* alpha, int64_t B,
+               int64_t N, int64_t C, float* out, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

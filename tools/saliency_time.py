@@ -40,6 +40,14 @@ alone), forward_after_ms, and the size of the kept q|k|v and lse buffers.
 times Swin3d.explain: Swin-T, 32 x 224^2, B = 1, the same medians: forward_ms (the plain eager forward), explain_rollout_ms,
 rollout_ms (the 12 ops.window_rollout_step calls and the 3 ops.merge_rollout_spread hops alone, on the q|k|v explain
 kept), forward_after_ms, and the size of the kept q|k|v.
+
+  python tools/saliency_time.py --family resnet3d [--out profiles/saliency_time_resnet3d.json]
+
+times ResNet3d.explain: ResNet3D-50, 32 x 224^2, B = 1, the same medians: forward_ms (the plain eager forward), then per
+layer (res5, res4) and method (gradcam, hirescam) explain_ms and its ratio to forward_ms of the same process; for res4
+also chain_ms (the data-gradient chain alone, on the activations explain kept), the chain's launches by kind (GEMM,
+col2im, relu_bwd) with each kind's share of the chain's device time (ops.OpRecorder events around every launch), and
+the bytes of the kept activations; forward_after_ms is the plain forward again at the end.
 """
 from __future__ import annotations
 
@@ -195,9 +203,67 @@ def swin(a) -> dict:
             "device": torch.cuda.get_device_name(0), "batches": {str(B): r}}
 
 
+def resnet3d(a) -> dict:
+    """ResNet3D-50, 32 x 224^2, B = 1: the plain eager forward, explain at both layers with both methods, and for res4
+    the data-gradient chain alone with its launches by kind"""
+    from vclip_amd import ops
+    from vclip_amd.build import source_hash
+    from vclip_amd.resnet3d import create_model
+    from vclip_amd.weights import make_synthetic_video
+
+    model = create_model(None, device=DEV).eval()
+    B = 1
+    video = torch.from_numpy(make_synthetic_video(B, 32, 224, seed=1)).to(DEV)
+
+    def forward():
+        model.forward_logits(video)
+
+    r = {"forward_ms": _median(forward, a.reps, a.warmup), "explain": {}}
+    for layer in model.EXPLAIN_LAYERS:
+        for method in model.EXPLAIN_METHODS:
+            def explain():
+                model.explain(video, method=method, target=0, layer=layer)
+
+            ms = _median(explain, a.reps, a.warmup)
+            r["explain"][f"{layer}.{method}"] = {"explain_ms": ms, "explain_over_forward": ms / r["forward_ms"]}
+        buf = model._explain_buffers(B, 32, 224, 224, layer, video.device)  # as the last explain left them
+        r["explain"][f"{layer}.kept_bytes"] = buf["kept_bytes"]
+    buf = model._explain_buffers(B, 32, 224, 224, "res4", video.device)
+
+    def chain():
+        model._explain_chain(buf, B)
+
+    r["res4_chain_ms"] = _median(chain, a.reps, a.warmup)
+    rec = ops.OpRecorder()
+    with ops.recording(rec):
+        for _ in range(a.reps):
+            chain()
+    torch.cuda.synchronize()
+    kinds = {}
+    for _, op, e0, e1, _, _ in rec.entries:
+        kind = "gemm" if op.startswith("cam.dgrad") else op.split(".", 1)[1]
+        k = kinds.setdefault(kind, {"launches": 0, "ms": 0.0})
+        k["launches"] += 1
+        k["ms"] += e0.elapsed_time(e1)
+    total = sum(k["ms"] for k in kinds.values())
+    r["res4_chain_launches"] = {kind: {"launches": k["launches"] // a.reps, "ms": k["ms"] / a.reps,
+                                       "share_of_chain": k["ms"] / total} for kind, k in kinds.items()}
+    r["res4_chain_over_forward"] = r["res4_chain_ms"] / r["forward_ms"]
+    r["forward_after_ms"] = _median(forward, a.reps, a.warmup)
+    print(f"ResNet3D-50 B = {B}: forward {r['forward_ms']:.3f} ms (after {r['forward_after_ms']:.3f}); "
+          + "; ".join(f"explain {k} {v['explain_ms']:.3f} ms ({v['explain_over_forward']:.2f}x)"
+                      for k, v in r["explain"].items() if isinstance(v, dict))
+          + f"; the res4 chain alone {r['res4_chain_ms']:.3f} ms: "
+          + ", ".join(f"{v['launches']} {k} launches {v['share_of_chain']:.0%}" for k, v in r["res4_chain_launches"].items())
+          + f"; kept activations {r['explain']['res4.kept_bytes'] / 1e6:.0f} MB (res4), "
+          f"{r['explain']['res5.kept_bytes'] / 1e6:.0f} MB (res5)", flush=True)
+    return {"model": "ResNet3D-50 32 x 224^2", "reps": a.reps, "warmup": a.warmup, "build": source_hash(),
+            "device": torch.cuda.get_device_name(0), "batches": {str(B): r}}
+
+
 def main() -> int:
     ap = argparse.ArgumentParser()
-    ap.add_argument("--family", choices=("vivit", "timesformer", "swin"), default="vivit")
+    ap.add_argument("--family", choices=("vivit", "timesformer", "swin", "resnet3d"), default="vivit")
     ap.add_argument("--out", default=None)
     ap.add_argument("--reps", type=int, default=15)
     ap.add_argument("--warmup", type=int, default=3)
@@ -207,8 +273,8 @@ def main() -> int:
                              f"saliency_time_{a.family}.json")
     if not torch.cuda.is_available():
         raise SystemExit("saliency_time.py needs a GPU")
-    if a.family in ("timesformer", "swin"):
-        res = timesformer(a) if a.family == "timesformer" else swin(a)
+    if a.family in ("timesformer", "swin", "resnet3d"):
+        res = {"timesformer": timesformer, "swin": swin, "resnet3d": resnet3d}[a.family](a)
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:
             json.dump(res, f, indent=1)
