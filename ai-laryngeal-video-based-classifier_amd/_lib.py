@@ -87,6 +87,9 @@ SIGNATURES = {
     "vc_relu_bwd": ([c_p, c_i64, c_p, c_int, c_i64, c_p, c_int, c_i64, c_i64, c_i64, c_p, c_i64, c_p], c_int),
     "vc_cam_weights": ([c_p, c_i64, c_i64, c_i64, c_i64, c_p, c_i64, c_p, c_p], c_int),
     "vc_cam_map": ([c_int, c_p, c_i64, c_p, c_i64, c_p, c_i64, c_i64, c_i64, c_p, c_p], c_int),
+    # ResNet50-LSTM saliency (csrc/frame_cam.hip)
+    "vc_frame_cam": ([c_p, c_i64, c_p, c_i64, c_i64, c_i64, c_i64, c_p, c_p, c_p], c_int),
+    "vc_frame_avgpool_bwd": ([c_p, c_i64, c_i64, c_i64, c_i64, c_p, c_i64, c_p], c_int),
     "vc_maxpool3d_bwd": ([c_p, c_i64, c_p, c_int, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_p, c_p, c_p, c_p, c_i64,
                           c_p], c_int),
     "vc_batchnorm_train_fwd": ([c_p, c_i64, c_i64, c_i64, c_p, c_p, c_f, c_f, c_p, c_p, c_p, c_int, c_i64, c_int, c_p,

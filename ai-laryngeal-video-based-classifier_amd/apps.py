@@ -650,6 +650,15 @@ LSTM_STREAM_CHUNK_HELP = (
     "writes frame_probabilities/<video>.csv.  128 is the smallest chunk within 5 %% of the best measured rate "
     "(4 videos of 256 frames: 41.0k frames/s at 9.2 GB peak; 32: 36.9k at 2.9 GB; 256: 41.9k at 17.1 GB, "
     "DESIGN.md section 5.11).")
+LSTM_SALIENCY_HELP = (
+    "off by default.  gradcam / hirescam: per-frame Grad-CAM (Selvaraju et al. 2017) or HiResCAM (Draelos & Carin 2020) "
+    "on the 2D backbone with the gradient taken through the head and the recurrence by exact BPTT "
+    "(VideoResNet50LSTM.explain), for --saliency_class at --saliency_layer; at res5 the two coincide.  Writes "
+    "saliency/<video>.npy (f32 [T, 7, 7] at res5, [T, 14, 14] at res4: the positive part of the map divided by its sum, "
+    "all zero when nothing is positive) and adds saliency_file, saliency_target and frame_importance (the map summed over "
+    "space, aligned with frame_indices) to the video's result row.  With --stream_chunk: whole recordings through the "
+    "explain session, no spatial maps; frame_probabilities/<video>.csv gains the columns relevance (the signed gradient x "
+    "input of the frame's pooled features) and importance (its positive part divided by the recording's sum).")
 LSTM_TBPTT_CHUNK_HELP = (
     "0 (default): off, the reference's training on --sequence_length sampled frames.  N >= 1: training and validation "
     "use every frame of every video; --batch_size videos advance in lockstep, at most N frames of each per round, "
@@ -675,6 +684,14 @@ def build_parser_lstm(inference: bool):
         p.add_argument("--videos_per_batch", type=int, default=LSTM_VIDEOS_PER_BATCH)
         # not in the reference either: whole-video streaming inference (forward_stream with the LSTM state carried)
         p.add_argument("--stream_chunk", type=int, default=0, help=LSTM_STREAM_CHUNK_HELP)
+        # not in the reference: which frames, and where in them, produced the prediction (VideoResNet50LSTM.explain)
+        p.add_argument("--saliency", type=str, default=None, choices=["gradcam", "hirescam"], help=LSTM_SALIENCY_HELP)
+        p.add_argument("--saliency_class", type=int, default=None, choices=[0, 1],
+                       help="with --saliency: 1 maps the evidence for referral (+logit), 0 for non_referral (-logit); "
+                            "absent: each video's predicted class")
+        p.add_argument("--saliency_layer", type=str, default="res5", choices=["res5", "res4"],
+                       help="with --saliency and without --stream_chunk: the backbone stage whose output is explained "
+                            "(res4: twice the spatial resolution, through the res5 bottlenecks' data gradients)")
         return p
     p = argparse.ArgumentParser(description="ResNet50-LSTM video classification training (libvclip, MI355X)")
     p.add_argument("--data_dir", type=str, default="dataset")  # resnet50-2d-lstm/main.py:22-62
@@ -1143,20 +1160,28 @@ def lstm_stream_rounds(sources, chunk, device):
         yield pp.lstm_inference_preprocess(frames), lens
 
 
-def lstm_stream_videos(model, sources, chunk, device):
+def lstm_stream_videos(model, sources, chunk, device, saliency_class="off"):
     """Whole-video inference over opened videos in lockstep (lstm_stream_rounds): one forward_stream call per
     round with the carried state; a finished video keeps its logit.
-    Returns (probabilities, one per video; per-frame probability lists, total_frames entries each)."""
+    Returns (probabilities, one per video; per-frame probability lists, total_frames entries each).
+    saliency_class None / 0 / 1 (instead of "off"): the rounds go through an explain session
+    (VideoResNet50LSTM.explain_stream_begin: the same launches, bit-identical logits) and its Explanation is returned
+    as a third value."""
     frame_probs = [[] for _ in sources]
     state, logits = None, None
+    sess = None if saliency_class == "off" else model.explain_stream_begin(len(sources))
     for clip, lens in lstm_stream_rounds(sources, chunk, device):
-        logits, state, fl = model.forward_stream(clip, lens, state, frame_logits=True)
+        if sess is None:
+            logits, state, fl = model.forward_stream(clip, lens, state, frame_logits=True)
+        else:
+            logits, fl = sess.push(clip, lens)
         fp = torch.sigmoid(fl.float()).reshape(-1).tolist()
         at = 0
         for b, n in enumerate(lens):
             frame_probs[b].extend(fp[at:at + n])
             at += n
-    return torch.sigmoid(logits.float()).reshape(-1).tolist(), frame_probs
+    probs = torch.sigmoid(logits.float()).reshape(-1).tolist()
+    return (probs, frame_probs) if sess is None else (probs, frame_probs, sess.finish(target=saliency_class))
 
 
 def _write_csv(rows, path):
@@ -1178,10 +1203,21 @@ def run_inference_lstm(argv=None):
     its own (clamped) frame count, go through one `forward_ragged`.  With --stream_chunk N >= 1 instead every
     video is read whole and the videos of a batch advance in lockstep through `forward_stream`, <= N frames each
     per call (lstm_stream_videos); frame_probabilities/<video>.csv and summary["stream_chunk"] are added.
+    With --saliency each batch goes through `explain(..., lengths=...)` instead (the same logits): saliency/<video>.npy
+    (f32 [T, h, w]) and the row fields saliency_file, saliency_target and frame_importance; with --stream_chunk through the
+    explain session: the relevance and importance columns of frame_probabilities/<video>.csv and saliency_target.
     Returns the summary dict (None when no video was found or none succeeded), with the experiment directory
     under "output_dir"."""
     import os
-    args = build_parser_lstm(inference=True).parse_args(argv)
+    parser = build_parser_lstm(inference=True)
+    args = parser.parse_args(argv)
+    if args.saliency is None and args.saliency_class is not None:
+        parser.error("--saliency_class needs --saliency gradcam or hirescam")
+    if args.saliency is None and args.saliency_layer != "res5":
+        parser.error("--saliency_layer needs --saliency gradcam or hirescam")
+    if args.saliency is not None and args.stream_chunk and args.saliency_layer != "res5":
+        parser.error("--saliency_layer does not apply with --stream_chunk: a streamed recording gets per-frame relevance, "
+                     "no spatial maps")
     exp = LstmExperimentLogger(os.path.join(args.output_dir, f"inference_{datetime.now().strftime('%Y%m%d_%H%M%S')}"),
                                prefix="inference")
     logger = exp.get_logger()
@@ -1211,12 +1247,25 @@ def run_inference_lstm(argv=None):
         print(f"Error processing video {path}: {str(e)}")
         return {"video_path": path, "prediction": None, "probability": None, "status": f"error: {str(e)}"}
 
+    def unique_name(folder, k, suffix):
+        name = os.path.basename(video_files[k])
+        if (folder / f"{name}{suffix}").exists():  # the same file name in two folders
+            name = f"{k}_{name}"
+        return f"{name}{suffix}"
+
     def flush(batch):
         if not batch:
             return
+        ex = None
         try:
+            clips, lens = torch.cat([c for _, c, _, _ in batch], dim=2), [len(i) for _, _, i, _ in batch]
             with torch.no_grad():
-                logits = model.forward_ragged(torch.cat([c for _, c, _, _ in batch], dim=2), [len(i) for _, _, i, _ in batch])
+                if args.saliency:
+                    ex = model.explain(clips, method=args.saliency, target=args.saliency_class, layer=args.saliency_layer,
+                                       lengths=lens)
+                    logits = ex.logits
+                else:
+                    logits = model.forward_ragged(clips, lens)
             probs = torch.sigmoid(logits.float()).reshape(-1).tolist()
         except Exception as e:  # noqa: BLE001 - the whole call failed: its videos get the error row
             for k, _, _, _ in batch:
@@ -1226,26 +1275,43 @@ def run_inference_lstm(argv=None):
             results[k] = {"video_path": video_files[k], "prediction": "referral" if p >= 0.5 else "non_referral",
                           "probability": float(p), "sampled_frames": len(idx), "total_frames": total,
                           "frame_indices": idx, "status": "success"}
+        if ex is not None:
+            sal_dir = out_dir / "saliency"
+            sal_dir.mkdir(exist_ok=True)
+            for b, (k, _, _, _) in enumerate(batch):
+                name = unique_name(sal_dir, k, ".npy")
+                np.save(sal_dir / name, ex.saliency[b].numpy())
+                results[k].update(saliency_file=f"saliency/{name}", saliency_target=int(ex.target[b]),
+                                  frame_importance=[float(v) for v in ex.temporal[b].tolist()])
 
     def flush_stream(batch):
         if not batch:
             return
+        ex = None
         try:
-            probs, frame_probs = lstm_stream_videos(model, [src for _, src in batch], args.stream_chunk, device)
+            if args.saliency:
+                probs, frame_probs, ex = lstm_stream_videos(model, [src for _, src in batch], args.stream_chunk, device,
+                                                            saliency_class=args.saliency_class)
+            else:
+                probs, frame_probs = lstm_stream_videos(model, [src for _, src in batch], args.stream_chunk, device)
         except Exception as e:  # noqa: BLE001 - the whole group failed: its videos get the error row
             for k, _ in batch:
                 results[k] = error_row(video_files[k], e)
             return
         fp_dir = out_dir / "frame_probabilities"
         fp_dir.mkdir(exist_ok=True)
-        for (k, src), p, fp in zip(batch, probs, frame_probs):
-            name = os.path.basename(video_files[k])
-            if (fp_dir / f"{name}.csv").exists():  # the same file name in two folders
-                name = f"{k}_{name}"
-            _write_csv([{"frame": i, "probability": v} for i, v in enumerate(fp)], fp_dir / f"{name}.csv")
+        for b, ((k, src), p, fp) in enumerate(zip(batch, probs, frame_probs)):
+            name = unique_name(fp_dir, k, ".csv")
+            rows = [{"frame": i, "probability": v} for i, v in enumerate(fp)]
+            if ex is not None:
+                for row, r, t in zip(rows, ex.frame_relevance[b].tolist(), ex.temporal[b].tolist()):
+                    row.update(relevance=r, importance=t)
+            _write_csv(rows, fp_dir / name)
             results[k] = {"video_path": video_files[k], "prediction": "referral" if p >= 0.5 else "non_referral",
                           "probability": float(p), "sampled_frames": src.total_frames, "total_frames": src.total_frames,
                           "frame_indices": "all", "status": "success"}
+            if ex is not None:
+                results[k]["saliency_target"] = int(ex.target[b])
 
     batch = []
     for k, path in enumerate(video_files):

@@ -893,6 +893,38 @@ def cam_map(mode: str, x: torch.Tensor, w: torch.Tensor, B: int, N: int, C: int,
     return out
 
 
+def frame_cam(x: torch.Tensor, g: torch.Tensor, N: int, P: int, C: int, out: torch.Tensor,
+              frame_rel: torch.Tensor) -> torch.Tensor:
+    """The class-activation map at the input of a per-frame average pool (vc_frame_cam): out f32 [N*P], out[n*P + p] =
+    (1/P) sum_c g[n, c] x[n*P + p, c] with x bf16 rows [>= N*P, >= C] and g f32 [>= N, >= C] the gradient with respect
+    to frame n's pooled features; frame_rel f32 [N] = the sum of frame n's P entries in order.  With P = 1 and x the
+    pooled features both are the signed gradient x input.  C % 8 == 0, C <= 4096."""
+    _dev(x, g, out, frame_rel)
+    _need(N >= 1 and P >= 1, "frame_cam: N and P must be >= 1")
+    _need(C % 8 == 0 and 0 < C <= 4096, "frame_cam: C % 8 == 0, C <= 4096")
+    _cl_rows(x, N * P, C, "frame_cam x")
+    _cl_rows(g, N, C, "frame_cam g", (torch.float32,))
+    _need(out.dtype == torch.float32 and out.is_contiguous() and out.numel() == N * P, "frame_cam out: f32 [N*P]")
+    _need(frame_rel.dtype == torch.float32 and frame_rel.is_contiguous() and frame_rel.numel() == N,
+          "frame_cam frame_rel: f32 [N]")
+    timed("frame_cam_kernel", "cam.frame_map", N * P * C * 2 + N * C * 4, "byte", _lib.call, "vc_frame_cam", _p(x),
+          x.stride(0), _p(g), g.stride(0), N, P, C, _p(out), _p(frame_rel), _stream(x))
+    return out
+
+
+def frame_avgpool_bwd(g: torch.Tensor, N: int, P: int, C: int, out: torch.Tensor) -> torch.Tensor:
+    """The adjoint of frame_avgpool (vc_frame_avgpool_bwd): out bf16 rows [>= N*P, >= C], out[n*P + p, c] =
+    bf16(g[n, c] / P) for g f32 [>= N, >= C]."""
+    _dev(g, out)
+    _need(N >= 1 and P >= 1, "frame_avgpool_bwd: N and P must be >= 1")
+    _need(C % 8 == 0 and C > 0, "frame_avgpool_bwd: C % 8 == 0")
+    _cl_rows(g, N, C, "frame_avgpool_bwd g", (torch.float32,))
+    _cl_rows(out, N * P, C, "frame_avgpool_bwd out")
+    timed("frame_avgpool_bwd_kernel", "cam.frame_seed", N * P * C * 2 + N * C * 4, "byte", _lib.call,
+          "vc_frame_avgpool_bwd", _p(g), g.stride(0), N, P, C, _p(out), out.stride(0), _stream(g))
+    return out
+
+
 # ---- train step (SURVEY.md §8 a16) -----------------------------------------------------------
 
 def attention_fwd_lse(qkv: torch.Tensor, B: int, S: int, H: int, out: torch.Tensor, lse: torch.Tensor,

@@ -23,6 +23,10 @@ Inference beyond the reference: `forward_ragged` batches videos of different len
 `init_state` / `forward_stream` carry nn.LSTM's (h, c) from call to call (vc_lstm_seq_fwd_state), so a
 recording of any length runs in chunks at bounded memory, with a logit after every frame.
 
+Saliency: `explain` is per-frame Grad-CAM / HiResCAM on the 2D backbone with the gradient taken through the head and
+the recurrence by exact BPTT (no weight gradients; csrc/frame_cam.hip), `explain_stream_begin` the per-frame relevance of
+whole recordings in chunks.
+
 Training beyond the reference: `forward_train_stream` is the train step on such chunks, over whole videos
 of different lengths with the state carried (autograd_ops.lstm_layer_state on vc_lstm_seq_fwd_train_state /
 vc_lstm_seq_bwd_state): the state it returns stays in the autograd graph (full BPTT across the chunks)
@@ -447,6 +451,199 @@ class VideoResNet50LSTM(torch.nn.Module):
         with torch.no_grad():
             return self._infer(x, lengths).clone()
 
+    # ---- explain: per-frame Grad-CAM / HiResCAM through the recurrence ------------------
+    EXPLAIN_METHODS = ResNet3d.EXPLAIN_METHODS
+    EXPLAIN_LAYERS = ResNet3d.EXPLAIN_LAYERS  # res2 / res3: out of scope
+    LSTM_DX_CFG = 5  # the 128 x 128 GEMM tile for every lstm_dx of explain: a frame's gradient row must not depend on
+    #                  how many rows share the launch (a streamed chunk against the whole recording)
+
+    def _explain_workspace(self, rows, nseq, Pl, Cl, device):
+        """explain's own buffers for `rows` frame rows in nseq sequences and a map of Pl positions x Cl channels per
+        frame; one key at a time, like _workspace (which it never touches)."""
+        key = (rows, nseq, Pl, Cl, str(device))
+        ws = getattr(self, "_explain_ws", None)
+        if ws is not None and ws["key"] == key:
+            return ws
+        H, M = self.hidden, _ru(rows, 256)
+        Np, Hp = _ru(4 * H, 128), _ru(H, 128)
+        f32, bf = torch.float32, torch.bfloat16
+        z = lambda r, c, dt=f32: torch.zeros(r, c, dtype=dt, device=device)  # noqa: E731
+        ws = dict(key=key, feat=z(M, 2048, bf), pre=z(M, Np), h_prev=z(M, Hp, bf), dpre=z(rows, 4 * H), dpb=z(M, Np, bf),
+                  hseq=[z(M, Hp, bf) for _ in range(2)], gates=[z(rows, 4 * H) for _ in range(self.layers)],
+                  c_seq=[z(rows, H) for _ in range(self.layers)], h_n=z(self.layers * nseq, H).view(self.layers, nseq, H), c_n=z(self.layers * nseq, H).view(self.layers, nseq, H),
+                  dxh=z(M, Hp), g=z(M, 2048), frame_rel=z(1, rows)[0], frame_map=z(1, rows)[0], map=z(1, rows * Pl)[0],
+                  map_rel=z(1, rows)[0], alpha=z(rows, Cl), cam_work=ops.cam_weights_work(rows, Cl, device),
+                  head=self._head_buffers(nseq, device))
+        self._explain_ws = ws
+        return ws
+
+    def _head_buffers(self, B, device):
+        z = lambda *s: torch.zeros(*s, dtype=torch.float32, device=device)  # noqa: E731
+        return dict(hid=z(B, HEAD_DIM), logits=z(B, 1), dlogits=z(B, 1), dh=z(B, self.hidden),
+                    dw1=z(HEAD_DIM, self.hidden), db1=z(HEAD_DIM), dw2=z(1, HEAD_DIM), db2=z(1))
+
+    def _head_gradient(self, pk, hb, h_top, target):
+        """The head on h_top f32 [B, H] with its hidden row kept, the targets (None: each sequence's predicted class, 1
+        when the logit is >= 0) and dh = d logit / d h_top in hb["dh"]: (logits clone, targets).  The head's weight
+        gradients land in scratch and are never read.
+        The gradient is always +z's.  Every launch after it is linear in the seed's sign, so target 0 (-z) is the finished
+        map times -1 on the host: the exact negation, which a seed of -1 would miss by last bits (the MFMA's
+        accumulation is not symmetric under a flip of every sign)."""
+        w1, b1, w2, b2 = pk["head"]
+        logits = ops.mlp_head_fwd(h_top, w1, b1, w2, b2, hb["logits"], hid=hb["hid"]).clone()
+        if target is None:
+            target = [int(v >= 0) for v in logits[:, 0].tolist()]
+        hb["dlogits"].fill_(1.0)
+        ops.mlp_head_bwd(h_top, w1, w2, hb["hid"], None, hb["dlogits"], hb["dh"], hb["dw1"], hb["db1"], hb["dw2"], hb["db2"])
+        return logits, target
+
+    def _lstm_dx(self, dpb, wt, out):
+        from .autograd_ops import _zeros_f32
+        return ops.gemm(dpb, wt, _zeros_f32(wt.shape[0], dpb.device), "bias_f32", out, cfg=self.LSTM_DX_CFG, op="lstm_dx")
+
+    @staticmethod
+    def _explain_targets(target, B):
+        from .vivit import VivitForVideoClassification
+        target, scalar = VivitForVideoClassification._check_targets(target, 2)
+        if target is not None:
+            target = target * B if scalar else target
+            if len(target) != B:
+                raise ValueError(f"explain: target has {len(target)} entries for {B} videos")
+        return target
+
+    @staticmethod
+    def _positive_share(rel: torch.Tensor) -> torch.Tensor:
+        """relu(rel) / its sum over one video's entries (all zero when nothing is positive), f32 like rel"""
+        pos = rel.double().clamp_min(0)
+        tot = pos.sum()
+        return (pos / tot if float(tot) > 0 else torch.zeros_like(pos)).float()
+
+    @torch.no_grad()
+    def explain(self, video: torch.Tensor, method: str = "gradcam", target=None, layer: str = "res5", lengths=None):
+        """The logit and which frames, and where in them, produced it: Grad-CAM (Selvaraju et al. 2017) or HiResCAM
+        (Draelos & Carin 2020) on the output of `layer` of the 2D backbone ("res5": H/32 x W/32 per frame, "res4":
+        H/16 x W/16), with the gradient taken through the head and the recurrence by exact BPTT.  The model has one
+        logit z: `target` 1 explains +z, 0 explains -z, None the predicted class (1 when z >= 0, the CLI's p >= 0.5);
+        an int, or a sequence / tensor of one int per video.
+
+        Dense: video [B, 3, T, H, W].  Ragged (`lengths` given): forward_ragged's layout, [1, 3, N, H, W] with the
+        frames of len(lengths) videos back to back, every length >= 1.
+
+        g_t = dz / d f_t (f_t the pooled features of frame t) comes from the head (vc_mlp_head_bwd with dlogits = 1; the
+        sign of target 0 is applied to the finished maps on the host, the exact negation), the top layer from dh_n, every lower layer through dx = dpre . W_ih (vc_lstm_seq_bwd_state + the lstm_dx GEMM,
+        fp32 out); no weight gradient is formed in the recurrence or the backbone.  Then, with A_t the layer's
+        activations in frame t and P its positions per frame:
+
+            "res5"  d z / d A_t[p, c] = g_t[c] / P at every position, so Grad-CAM and HiResCAM coincide:
+                    map[t, p] = (1/P) sum_c g_t[c] A_t[p, c] from the fp32 g_t (vc_frame_cam).  Both methods run the
+                    same launches there: their maps are bit-identical.
+            "res4"  the res5 rows are seeded with bf16(g_t[c] / P) (vc_frame_avgpool_bwd) and ResNet3d._explain_chain walks
+                    back to res4: "hirescam" sum_c G[t, p, c] A[t, p, c]; "gradcam" sum_c alpha_t[c] A[t, p, c] with
+                    alpha_t the mean of G over the positions of FRAME t (the backbone is a 2D network applied per frame:
+                    each frame is its own image).
+            frame_relevance[t] = sum_c g_t[c] f_t[c], the signed gradient x input on the pooled features: the temporal
+                    attribution, which needs no spatial map (vc_frame_cam with P = 1).
+
+        Returns vivit.Explanation: `logits` f32 [B, 1] on the device, bit-identical to model(video) / forward_ragged
+        (the recurrence kernels are instantiations of one step loop); on the host `token_relevance` f32 [B, T*h*w], the
+        SIGNED map in the row order (t*h + y)*w + x, `saliency` f32 [B, T, h, w] = relu(map) / its per-video sum (all
+        zero when nothing is positive), `temporal` f32 [B, T] (saliency summed over space), `frame_relevance` f32 [B, T]
+        (signed), `method`, and `target`, B ints in {0, 1}.  Ragged: token_relevance, saliency, temporal and
+        frame_relevance are lists of per-video tensors ([n*h*w], [n, h, w], [n], [n]).
+
+        Runs the eager inference launches with the backbone activations after the layer, each LSTM layer's gates and
+        cell states and the head's hidden row kept in buffers of its own (cached per shape); the forward's workspaces
+        and packed weights are untouched.  Refuses (no fallback): training mode, CPU tensors, an unknown method or
+        layer ("res2" / "res3" are not supported), a target outside {0, 1} or of the wrong length, a video that is
+        not [B, 3, T, H, W] (ragged: [1, 3, N, H, W] with lengths >= 1 that sum to N)."""
+        from .vivit import Explanation
+        if method not in self.EXPLAIN_METHODS:
+            raise ValueError(f"explain: method must be one of {self.EXPLAIN_METHODS}, not {method!r}")
+        if layer not in self.EXPLAIN_LAYERS:
+            raise ValueError(f"explain: layer must be one of {self.EXPLAIN_LAYERS}, not {layer!r}")
+        if self.training:
+            raise RuntimeError("explain: inference only; call model.eval() first")
+        if not isinstance(video, torch.Tensor) or video.device.type != "cuda":
+            raise RuntimeError("explain runs on the GPU only: move the clip batch to cuda")
+        if lengths is None:
+            if video.dim() != 5 or video.shape[1] != 3 or video.shape[0] < 1 or video.shape[2] < 1:
+                raise ValueError(f"video {tuple(video.shape)} must be [B, 3, T, H, W]")
+            nseq = video.shape[0]
+        else:
+            lengths = tuple(int(n) for n in lengths)
+            if video.dim() != 5 or video.shape[0] != 1 or video.shape[1] != 3:
+                raise ValueError(f"video {tuple(video.shape)} must be [1, 3, N, H, W]: the frames of all videos back to back")
+            if not lengths or min(lengths) < 1 or sum(lengths) != video.shape[2]:
+                raise ValueError(f"lengths {lengths} must be >= 1 and sum to the {video.shape[2]} frames of video")
+            nseq = len(lengths)
+        target = self._explain_targets(target, nseq)
+        x = video.contiguous().float() if video.dtype != torch.float32 else video.contiguous()
+        Bb, _, T, Hh, Ww = x.shape
+        rows, dev, H = Bb * T, x.device, self.hidden
+        bb = self.backbone
+        pk, bpk = self._pack(dev), bb._pack(dev)
+        buf = bb._explain_buffers(Bb, T, Hh, Ww, layer, dev)
+        bb._pack_transposed(bpk, buf["stage"] + 1)
+        # forward: the inference launches, with what the backward reads kept
+        act, _, (_, h, w), Cf, _ = bb.forward_features(x, keep=buf)
+        P, (_, hl, wl), Cl = h * w, buf["grid"], buf["C"]
+        Pl = hl * wl
+        ws = self._explain_workspace(rows, nseq, Pl, Cl, dev)
+        ops.frame_avgpool(act, rows, P, Cf, ws["feat"])
+        inp = ws["feat"]
+        dense_T = T if lengths is None else None
+        for l, L in enumerate(pk["layers"]):
+            hseq = ws["hseq"][l & 1]
+            ops.gemm(inp, L["wb"], L["b"], "bias_f32", ws["pre"], op="lstm_ih")
+            ops.lstm_seq_fwd_train_state(ws["pre"], lengths, H, L["w_hh_t"], hseq, ws["h_n"][l], ws["c_n"][l], ws["gates"][l],
+                                         ws["c_seq"][l], ws["h_prev"], T=dense_T)
+            inp = hseq
+        logits, target = self._head_gradient(pk, ws["head"], ws["h_n"][self.layers - 1], target)
+        # backward: exact BPTT from the top layer's h_n down to the pooled features, fp32 throughout
+        dh_seq = None
+        for l in range(self.layers - 1, -1, -1):
+            L = pk["layers"][l]
+            ops.lstm_seq_bwd_state(ws["gates"][l], ws["c_seq"][l], nseq, lengths, H, L["w_hh"], ws["dpre"], ws["dpb"],
+                                   dh_seq=dh_seq, dh_n=ws["head"]["dh"] if dh_seq is None else None, T=dense_T)
+            dh_seq = self._lstm_dx(ws["dpb"], L["wt"], ws["g"] if l == 0 else ws["dxh"])
+        g = ws["g"]
+        ops.frame_cam(ws["feat"], g, rows, 1, Cf, ws["frame_map"], ws["frame_rel"])
+        if not buf["chain"]:  # res5: both methods, the same launch
+            ops.frame_cam(buf["x"], g, rows, P, Cf, ws["map"], ws["map_rel"])
+        else:
+            ops.frame_avgpool_bwd(g, rows, P, Cf, buf["seed"])
+            G = bb._explain_chain(buf, Bb)
+            if method == "gradcam":
+                ops.cam_weights(G, rows, Pl, Cl, ws["cam_work"], ws["alpha"])
+                ops.cam_map("gradcam", buf["x"], ws["alpha"], rows, Pl, Cl, ws["map"])
+            else:
+                ops.cam_map("hirescam", buf["x"], G, rows, Pl, Cl, ws["map"])
+        both = torch.cat([ws["map"], ws["frame_rel"]]).cpu()  # the one copy; the rest is host bookkeeping
+        rel, frel = both[: rows * Pl], both[rows * Pl:]
+        sign = torch.tensor([1.0 if t else -1.0 for t in target]).repeat_interleave(
+            torch.tensor([T] * nseq if lengths is None else lengths))  # per frame row: target 0 explains -z
+        rel, frel = (rel.reshape(rows, Pl) * sign[:, None]).reshape(-1), frel * sign
+        if lengths is None:
+            rel, frel = rel.reshape(nseq, T * Pl).contiguous(), frel.reshape(nseq, T).contiguous()
+            sal = torch.stack([self._positive_share(r) for r in rel]).reshape(nseq, T, hl, wl)
+            return Explanation(logits, rel, sal, sal.sum(dim=(2, 3)), method, target=target, frame_relevance=frel)
+        rels, frels, sals, r0 = [], [], [], 0
+        for n in lengths:
+            rels.append(rel[r0 * Pl: (r0 + n) * Pl].clone())
+            frels.append(frel[r0: r0 + n].clone())
+            sals.append(self._positive_share(rels[-1]).reshape(n, hl, wl))
+            r0 += n
+        return Explanation(logits, rels, sals, [s.sum(dim=(1, 2)) for s in sals], method, target=target,
+                           frame_relevance=frels)
+
+    def explain_stream_begin(self, B: int) -> "ExplainSession":
+        """A whole-recording explanation in chunks, for B recordings: see ExplainSession."""
+        if self.training:
+            raise RuntimeError("explain: inference only; call model.eval() first")
+        if not isinstance(B, int) or B < 1:
+            raise ValueError("explain_stream_begin: B must be an int >= 1")
+        return ExplainSession(self, B)
+
     def _forward_train(self, video: torch.Tensor) -> torch.Tensor:
         B, _, T = video.shape[:3]
         return self._forward_tail(self.features(video, train_bn=not self.freeze_backbone_bn)[: B * T], B, T)
@@ -474,6 +671,118 @@ class VideoResNet50LSTM(torch.nn.Module):
         self.last_keep = {"lstm": keeps, "head": hkeep}
         return A.mlp_head(h_last, self.P("classifier.0.weight"), self.P("classifier.0.bias"),
                           self.P("classifier.3.weight"), self.P("classifier.3.bias"), hkeep)
+
+
+class ExplainSession:
+    """Which frames of whole recordings produced the logit, at bounded GPU memory per chunk
+    (VideoResNet50LSTM.explain_stream_begin(B)):
+
+        sess = model.explain_stream_begin(B)
+        for video, lengths in chunks:                  # forward_stream's arguments
+            logits, frame_logits = sess.push(video, lengths)
+        ex = sess.finish(target=None)
+
+    push runs forward_stream's launches (the recurrence in its saving instantiation) and returns (logits f32 [B, 1],
+    frame logits f32 [N, 1]), bit-identical to forward_stream(video, lengths, state, frame_logits=True); the state is
+    carried inside the session.  Per chunk it keeps the bf16 pooled features, each layer's gates and cell states, each
+    layer's incoming c0 and the row layout: 2 * 2048 + layers * (16 + 4) * hidden bytes per frame, 14336 B (14 KB) at
+    hidden 256 and two layers, plus layers * B * hidden * 4 bytes of c0 per chunk -- a 10-minute recording at 30
+    frames/s is 258 MB.  No backbone activation is kept: there are no spatial maps in this mode.
+
+    finish walks the chunks in reverse: the head's dh enters at each recording's h_n, vc_lstm_seq_bwd_state chains dh0
+    / dc0 into the previous chunk's dh_n / dc_n (a recording that paused with length 0 passes them through), and each
+    chunk's g goes through vc_frame_cam with P = 1.  It returns vivit.Explanation with `logits` f32 [B, 1] on the
+    device, `frame_relevance` a list of B f32 tensors (one entry per frame the recording pushed, signed; bit-identical
+    to explain(..., lengths=...) on the whole recordings), `temporal` its positive part divided by its per-recording
+    sum (all zero when nothing is positive), `target`, method "frame_relevance", and token_relevance = saliency =
+    None.  One finish per session; push after it is refused."""
+
+    def __init__(self, model: "VideoResNet50LSTM", B: int):
+        self.model, self.B = model, B
+        self.state = None
+        self.chunks = []
+        self.done = False
+
+    @torch.no_grad()
+    def push(self, video: torch.Tensor, lengths):
+        m = self.model
+        if self.done:
+            raise RuntimeError("explain session: finish() was called; begin a new session")
+        if m.training:
+            raise RuntimeError("explain: inference only; call model.eval() first")
+        x, lengths, B = m._stream_args(video, lengths, self.state)
+        if B != self.B:
+            raise ValueError(f"explain session: {B} lengths for the session's {self.B} recordings")
+        N, dev, H, nl = x.shape[2], x.device, m.hidden, m.layers
+        pk = m._pack(dev)
+        act, _, (_, h, w), Cf, _ = m.backbone.forward_features(x)
+        M, Hp = _ru(N, 256), _ru(H, 128)
+        f32, bf = torch.float32, torch.bfloat16
+        z = lambda r, c, dt=f32: torch.zeros(r, c, dtype=dt, device=dev)  # noqa: E731
+        feat = z(M, Cf, bf)
+        ops.frame_avgpool(act, N, h * w, Cf, feat)
+        pre, hseq, h_prev, hall = z(M, _ru(4 * H, 128)), [z(M, Hp, bf) for _ in range(2)], z(M, Hp, bf), z(M, H)
+        old = self.state
+        new = LstmState(torch.empty(nl, B, H, dtype=f32, device=dev), torch.empty(nl, B, H, dtype=f32, device=dev))
+        gates, c_seq = [z(N, 4 * H) for _ in range(nl)], [z(N, H) for _ in range(nl)]
+        inp = feat
+        for l, L in enumerate(pk["layers"]):
+            h0, c0 = (None, None) if old is None else (old.h[l], old.c[l])
+            ops.gemm(inp, L["wb"], L["b"], "bias_f32", pre, op="lstm_ih")
+            ops.lstm_seq_fwd_train_state(pre, lengths, H, L["w_hh_t"], hseq[l & 1], new.h[l], new.c[l], gates[l], c_seq[l],
+                                         h_prev, h0=h0, c0=c0)
+            if l == nl - 1:  # the unrounded h of every frame for the frame logits: the inference instantiation again
+                ops.lstm_seq_fwd_state(pre, lengths, H, L["w_hh_t"], h_prev, torch.empty_like(new.h[l]),
+                                       torch.empty_like(new.c[l]), h0=h0, c0=c0, h_all=hall)
+            inp = hseq[l & 1]
+        w1, b1, w2, b2 = pk["head"]
+        logits = ops.mlp_head_fwd(new.h[nl - 1], w1, b1, w2, b2, torch.empty(B, 1, dtype=f32, device=dev))
+        frames = ops.mlp_head_fwd(hall[:N], w1, b1, w2, b2, torch.empty(N, 1, dtype=f32, device=dev))
+        self.chunks.append(dict(lengths=lengths, feat=feat[:N], gates=gates, c_seq=c_seq,
+                                c0=None if old is None else old.c))
+        self.state = new
+        return logits, frames
+
+    @torch.no_grad()
+    def finish(self, target=None):
+        from .vivit import Explanation
+        m = self.model
+        if self.done:
+            raise RuntimeError("explain session: finish() was already called")
+        if not self.chunks:
+            raise RuntimeError("explain session: finish() before any push()")
+        B, H, nl = self.B, m.hidden, m.layers
+        target = m._explain_targets(target, B)
+        dev = self.state.h.device
+        pk = m._pack(dev)
+        hb = m._head_buffers(B, dev)
+        logits, target = m._head_gradient(pk, hb, self.state.h[nl - 1], target)
+        f32 = torch.float32
+        dH, dC = torch.zeros(nl, B, H, dtype=f32, device=dev), torch.zeros(nl, B, H, dtype=f32, device=dev)
+        dH[nl - 1].copy_(hb["dh"])
+        per = [[] for _ in range(B)]  # per recording, its chunks' relevance, last chunk first
+        for ch in reversed(self.chunks):
+            N, lengths = ch["feat"].shape[0], ch["lengths"]
+            M = _ru(N, 256)
+            dpre = torch.empty(N, 4 * H, dtype=f32, device=dev)
+            dpb = torch.zeros(M, _ru(4 * H, 128), dtype=torch.bfloat16, device=dev)
+            dh_seq = None
+            for l in range(nl - 1, -1, -1):
+                L = pk["layers"][l]
+                ops.lstm_seq_bwd_state(ch["gates"][l], ch["c_seq"][l], B, lengths, H, L["w_hh"], dpre, dpb, dh_seq=dh_seq,
+                                       dh_n=dH[l], dc_n=dC[l], c0=None if ch["c0"] is None else ch["c0"][l], dh0=dH[l],
+                                       dc0=dC[l])
+                dh_seq = m._lstm_dx(dpb, L["wt"], torch.empty(M, L["wt"].shape[0], dtype=f32, device=dev))
+            frel = torch.empty(N, dtype=f32, device=dev)
+            ops.frame_cam(ch["feat"], dh_seq, N, 1, ch["feat"].shape[1], torch.empty(N, dtype=f32, device=dev), frel)
+            frel, r0 = frel.cpu(), 0
+            for b, n in enumerate(lengths):
+                per[b].append(frel[r0: r0 + n] * (1.0 if target[b] else -1.0))  # target 0 explains -z
+                r0 += n
+        self.done, self.chunks = True, []
+        frels = [torch.cat(list(reversed(p))).contiguous() for p in per]
+        return Explanation(logits, None, None, [m._positive_share(r) for r in frels], "frame_relevance", target=target,
+                           frame_relevance=frels)
 
 
 def create_model(hidden_size: int = 256, num_layers: int = 2, dropout: float = 0.5, device="cuda",

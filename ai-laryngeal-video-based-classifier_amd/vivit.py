@@ -82,12 +82,15 @@ class Explanation:
     `token_relevance` f32 [B, S] (column 0 is CLS), `saliency` f32 [B, T/kt, H/kh, W/kw] (the patch tokens'
     relevance divided by its per-clip sum) and `temporal` f32 [B, T/kt] (saliency summed over space) on the host.
     `target`: the B class indices a class-specific method ("grad_rollout"; ResNet3d.explain's Grad-CAM / HiResCAM, whose
-    `token_relevance` is the signed map with no CLS column) explained, None for the others."""
+    `token_relevance` is the signed map with no CLS column) explained, None for the others.
+    `frame_relevance`: VideoResNet50LSTM.explain's signed gradient x input per frame, f32 [B, T] on the host (a list
+    of per-video tensors for ragged batches and streamed recordings); None for every other family."""
 
-    def __init__(self, logits, token_relevance, saliency, temporal, method, target=None):
+    def __init__(self, logits, token_relevance, saliency, temporal, method, target=None, frame_relevance=None):
         self.logits, self.token_relevance, self.saliency, self.temporal = logits, token_relevance, saliency, temporal
         self.method = method
         self.target = target
+        self.frame_relevance = frame_relevance
 
 
 class ClassifierOutput:

@@ -1,5 +1,6 @@
-"""Drop-in for the reference's `resnet50-2d-lstm/inference.py` (same flags, plus `--videos_per_batch`):
-runs on libvclip / MI355X, several videos per forward.
+"""Drop-in for the reference's `resnet50-2d-lstm/inference.py` (same flags, plus `--videos_per_batch`, `--stream_chunk`
+and `--saliency {gradcam,hirescam} [--saliency_class {0,1}] [--saliency_layer {res5,res4}]`): runs on libvclip / MI355X,
+several videos per forward; with `--saliency` also which frames, and where in them, produced each prediction.
 
     python cli/resnet50-2d-lstm/inference.py <the reference's arguments>
 """

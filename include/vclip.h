@@ -972,6 +972,23 @@ int vc_cam_weights(const uint16_t* g, int64_t ldg, int64_t B, int64_t N, int64_t
 int vc_cam_map(int mode, const uint16_t* x, int64_t ldx, const uint16_t* g, int64_t ldg, const float* alpha, int64_t B,
                int64_t N, int64_t C, float* out, hipStream_t stream);
 
+/* ---- ResNet50-LSTM saliency: per-frame CAM through the recurrence (frame_cam.hip; VideoResNet50LSTM.explain) ----
+ * x / out are channels-last bf16 rows n*P + p (frame n, position p) as above; g is the f32 gradient of the logit with
+ * respect to the pooled features of frame n, rows of stride ldg >= C, ldg % 4 == 0, 16-B aligned.  Only rows < N*P
+ * (g: < N) and columns < C are read or written.  No atomics, fixed summation order: bit-reproducible, and frame n's
+ * outputs do not depend on N. */
+
+/* map f32 [N*P]: map[n*P + p] = (1/P) sum_c g[n][c] x[n*P + p][c], the class-activation map at the input of the
+ * per-frame average pool (the gradient there is g[n][c] / P at every position, so Grad-CAM and HiResCAM coincide);
+ * frame_rel f32 [N]: frame_rel[n] = sum_p map[n*P + p] in p order.  With P = 1 and x the pooled features [N][C],
+ * frame_rel[n] = map[n] = sum_c g[n][c] x[n][c], the signed gradient x input.  Any P >= 1; C <= 4096. */
+int vc_frame_cam(const uint16_t* x, int64_t ldx, const float* g, int64_t ldg, int64_t N, int64_t P, int64_t C, float* map,
+                 float* frame_rel, hipStream_t stream);
+
+/* out[n*P + p][c] = bf16(g[n][c] / P): the adjoint of vc_frame_avgpool, N*P rows. */
+int vc_frame_avgpool_bwd(const float* g, int64_t ldg, int64_t N, int64_t P, int64_t C, uint16_t* out, int64_t ldo,
+                         hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

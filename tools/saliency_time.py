@@ -48,6 +48,14 @@ layer (res5, res4) and method (gradcam, hirescam) explain_ms and its ratio to fo
 also chain_ms (the data-gradient chain alone, on the activations explain kept), the chain's launches by kind (GEMM,
 col2im, relu_bwd) with each kind's share of the chain's device time (ops.OpRecorder events around every launch), and
 the bytes of the kept activations; forward_after_ms is the plain forward again at the end.
+
+  python tools/saliency_time.py --family lstm [--out profiles/saliency_time_lstm.json]
+
+times VideoResNet50LSTM.explain: ResNet50-LSTM (hidden 256, two layers), 32 x 224^2, B = 1, the same medians: forward_ms
+(`model(video)`, the eager inference path), then per layer (res5, res4) and method explain_ms and its ratio to forward_ms of
+the same process; bptt_ms (the head's and the recurrence's backward with the two lstm_dx GEMMs and the P = 1 vc_frame_cam,
+alone, on what explain kept), for res4 chain_ms (the backbone's data-gradient chain alone), the bytes of the kept backbone
+activations, and forward_after_ms.
 """
 from __future__ import annotations
 
@@ -261,9 +269,64 @@ def resnet3d(a) -> dict:
             "device": torch.cuda.get_device_name(0), "batches": {str(B): r}}
 
 
+def lstm(a) -> dict:
+    """ResNet50-LSTM, 32 x 224^2, B = 1: model(video), explain at both layers with both methods, the recurrence's
+    backward alone and, for res4, the backbone's data-gradient chain alone"""
+    from vclip_amd import ops
+    from vclip_amd.build import source_hash
+    from vclip_amd.resnet50_lstm import create_model
+    from vclip_amd.weights import make_synthetic_video
+
+    model = create_model(device=DEV).eval()
+    B, T = 1, 32
+    video = torch.from_numpy(make_synthetic_video(B, T, 224, seed=1)).to(DEV)
+
+    def forward():
+        model(video)
+
+    r = {"forward_ms": _median(forward, a.reps, a.warmup), "explain": {}}
+    for layer in model.EXPLAIN_LAYERS:
+        for method in model.EXPLAIN_METHODS:
+            def explain():
+                model.explain(video, method=method, target=1, layer=layer)
+
+            ms = _median(explain, a.reps, a.warmup)
+            r["explain"][f"{layer}.{method}"] = {"explain_ms": ms, "explain_over_forward": ms / r["forward_ms"]}
+        buf = model.backbone._explain_buffers(B, T, 224, 224, layer, video.device)  # as the last explain left them
+        r["explain"][f"{layer}.kept_bytes"] = buf["kept_bytes"]
+    buf = model.backbone._explain_buffers(B, T, 224, 224, "res4", video.device)
+    ws, pk, H = model._explain_ws, model._packed, model.hidden
+
+    def bptt():
+        model._head_gradient(pk, ws["head"], ws["h_n"][model.layers - 1], [1] * B)
+        dh_seq = None
+        for l in range(model.layers - 1, -1, -1):
+            L = pk["layers"][l]
+            ops.lstm_seq_bwd_state(ws["gates"][l], ws["c_seq"][l], B, None, H, L["w_hh"], ws["dpre"], ws["dpb"], dh_seq=dh_seq,
+                                   dh_n=ws["head"]["dh"] if dh_seq is None else None, T=T)
+            dh_seq = model._lstm_dx(ws["dpb"], L["wt"], ws["g"] if l == 0 else ws["dxh"])
+        ops.frame_cam(ws["feat"], ws["g"], B * T, 1, 2048, ws["frame_map"], ws["frame_rel"])
+
+    def chain():
+        model.backbone._explain_chain(buf, B)
+
+    r["bptt_ms"] = _median(bptt, a.reps, a.warmup)
+    r["res4_chain_ms"] = _median(chain, a.reps, a.warmup)
+    r["res4_chain_over_forward"] = r["res4_chain_ms"] / r["forward_ms"]
+    r["forward_after_ms"] = _median(forward, a.reps, a.warmup)
+    print(f"ResNet50-LSTM B = {B}, T = {T}: forward {r['forward_ms']:.3f} ms (after {r['forward_after_ms']:.3f}); "
+          + "; ".join(f"explain {k} {v['explain_ms']:.3f} ms ({v['explain_over_forward']:.2f}x)"
+                      for k, v in r["explain"].items() if isinstance(v, dict))
+          + f"; head + recurrence backward alone {r['bptt_ms']:.3f} ms, the res4 chain alone {r['res4_chain_ms']:.3f} ms; "
+          f"kept activations {r['explain']['res4.kept_bytes'] / 1e6:.0f} MB (res4), "
+          f"{r['explain']['res5.kept_bytes'] / 1e6:.0f} MB (res5)", flush=True)
+    return {"model": "ResNet50-LSTM 32 x 224^2", "reps": a.reps, "warmup": a.warmup, "build": source_hash(),
+            "device": torch.cuda.get_device_name(0), "batches": {str(B): r}}
+
+
 def main() -> int:
     ap = argparse.ArgumentParser()
-    ap.add_argument("--family", choices=("vivit", "timesformer", "swin", "resnet3d"), default="vivit")
+    ap.add_argument("--family", choices=("vivit", "timesformer", "swin", "resnet3d", "lstm"), default="vivit")
     ap.add_argument("--out", default=None)
     ap.add_argument("--reps", type=int, default=15)
     ap.add_argument("--warmup", type=int, default=3)
@@ -273,8 +336,8 @@ def main() -> int:
                              f"saliency_time_{a.family}.json")
     if not torch.cuda.is_available():
         raise SystemExit("saliency_time.py needs a GPU")
-    if a.family in ("timesformer", "swin", "resnet3d"):
-        res = {"timesformer": timesformer, "swin": swin, "resnet3d": resnet3d}[a.family](a)
+    if a.family in ("timesformer", "swin", "resnet3d", "lstm"):
+        res = {"timesformer": timesformer, "swin": swin, "resnet3d": resnet3d, "lstm": lstm}[a.family](a)
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:
             json.dump(res, f, indent=1)
