@@ -90,6 +90,10 @@ SIGNATURES = {
     # ResNet50-LSTM saliency (csrc/frame_cam.hip)
     "vc_frame_cam": ([c_p, c_i64, c_p, c_i64, c_i64, c_i64, c_i64, c_p, c_p, c_p], c_int),
     "vc_frame_avgpool_bwd": ([c_p, c_i64, c_i64, c_i64, c_i64, c_p, c_i64, c_p], c_int),
+    # saliency faithfulness (csrc/perturb.hip)
+    "vc_perturb_clips": ([c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_int, c_i64, c_i64, c_i64, c_i64, c_int,
+                          c_p, c_p], c_int),
+    "vc_gaussian_blur_planes": ([c_p, c_i64, c_i64, c_i64, c_i64, c_f, c_p, c_p, c_p], c_int),
     "vc_maxpool3d_bwd": ([c_p, c_i64, c_p, c_int, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_p, c_p, c_p, c_p, c_i64,
                           c_p], c_int),
     "vc_batchnorm_train_fwd": ([c_p, c_i64, c_i64, c_i64, c_p, c_p, c_f, c_f, c_p, c_p, c_p, c_int, c_i64, c_int, c_p,

@@ -243,8 +243,30 @@ RESNET3D_SALIENCY_HELP = (
     "--saliency_layer.  Writes <video>_saliency.npy (f32 [T, H/32, W/32] at res5, [T, H/16, W/16] at res4; the positive "
     "part of the map, sums to 1, or all zero when the map has nothing positive) beside the result JSON, which gains a "
     "\"saliency\" object with each frame's importance and its source-frame index.")
+SALIENCY_CHECK_HELP = (
+    "with --saliency: score the map with the perturbation test (vclip_amd.faithfulness) in STEPS steps: the class score "
+    "as the map's cells are deleted from the clip and inserted into a zero clip in the map's order, and deleted in a "
+    "random order.  The result JSON's \"saliency\" object gains a \"faithfulness\" object with the three curves and "
+    "their areas (deletion_gain = random_deletion_auc - deletion_auc: positive when the map beats chance).")
 # per family: the --saliency methods that take --saliency_class
 CLASS_SPECIFIC_SALIENCY = {"vivit": ("grad_rollout",), "resnet3d": ("gradcam", "hirescam")}
+
+
+def _positive_int(text: str) -> int:
+    v = int(text)  # a ValueError is argparse's "invalid value"
+    if v < 1:
+        raise argparse.ArgumentTypeError(f"{text}: must be at least 1")
+    return v
+
+
+class _SaliencyCheckParser(argparse.ArgumentParser):
+    """The inference parser as run_inference builds it: --saliency_check without --saliency is an error"""
+
+    def parse_args(self, args=None, namespace=None):
+        a = super().parse_args(args, namespace)
+        if getattr(a, "saliency_check", None) is not None and getattr(a, "saliency", None) is None:
+            self.error("--saliency_check needs --saliency")
+        return a
 
 
 def _temporal_patch(model) -> int:
@@ -265,7 +287,8 @@ def build_parser(fam: Family, inference: bool, saliency: bool = False):
     their `explain` existed."""
     if fam.name == "lstm":
         return build_parser_lstm(inference)
-    p = argparse.ArgumentParser(description=f"{fam.name} video classifier (libvclip, MI355X)")
+    cls = _SaliencyCheckParser if inference and saliency else argparse.ArgumentParser
+    p = cls(description=f"{fam.name} video classifier (libvclip, MI355X)")
     if inference:
         p.add_argument("--video_path", type=str, required=True)
         p.add_argument("--model_path", type=str, required=True)
@@ -302,6 +325,9 @@ def build_parser(fam: Family, inference: bool, saliency: bool = False):
             p.add_argument("--saliency_layer", type=str, default="res5", choices=["res5", "res4"],
                            help="with --saliency: the stage whose output is explained (res4: twice the spatial "
                                 "resolution, through the res5 data-gradient chain)")
+        if saliency:
+            p.add_argument("--saliency_check", type=_positive_int, default=None, metavar="STEPS",
+                           help=SALIENCY_CHECK_HELP)
         return p
     required = fam.name in ("swin", "resnet3d")
     p.add_argument("--data_dir", type=str, required=True)
@@ -616,6 +642,18 @@ def run_inference(fam_name, argv=None):
             if not sal.any():  # the map has nothing positive: no evidence for the class at this layer
                 res["saliency"]["empty"] = True
         logger.info(f"Saliency ({saliency}): {out / npy}, most important tubelet {int(ex.temporal[0].argmax())}")
+        if args.saliency_check:
+            # does the label move when what the map points at is taken away?  scored for the class the map explains
+            from .faithfulness import faithfulness
+            chk = faithfulness(model, x, ex, steps=args.saliency_check, baseline="zero",
+                               target=pred if ex.target is None else ex.target[0])
+            areas = {k: float(chk[k][0]) for k in ("deletion_auc", "insertion_auc", "random_deletion_auc", "deletion_gain")}
+            res["saliency"]["faithfulness"] = dict(
+                steps=chk["steps"], baseline=chk["baseline"], target_class=chk["target"][0], **areas,
+                fractions=[float(v) for v in chk["deletion"].fractions],
+                **{k: [float(v) for v in chk[k].score[0]] for k in ("deletion", "insertion", "random_deletion")})
+            logger.info(f"Saliency check ({args.saliency_check} steps): deletion AUC {areas['deletion_auc']:.4f}, "
+                        f"random-order {areas['random_deletion_auc']:.4f}, insertion AUC {areas['insertion_auc']:.4f}")
     with open(out / f"{Path(args.video_path).stem}_result.json", "w") as f:
         json.dump(res, f, indent=4)
     return res

@@ -1699,3 +1699,80 @@ def mlp_head_bwd(h, w1, w2, hid, keep, dlogits, dh, dw1, db1, dw2, db2):
           _p(w1), _p(w2), _p(hid), _p(keep) if keep is not None else None, _p(dlogits), B, H, H1, nl, _p(dh), _p(dw1),
           _p(db1), _p(dw2), _p(db2), _stream(h))
     return dh
+
+
+# ---- saliency faithfulness (csrc/perturb.hip; vclip_amd/faithfulness.py) ----
+CLIP_LAYOUT = {"btchw": 0, "bcthw": 1}
+PERTURB_MODE = {"deletion": 0, "insertion": 1}
+
+
+def gaussian_taps(ksize: int, sigma: float) -> torch.Tensor:
+    """The f32 taps vc_gaussian_blur_planes uses: exp(-d^2 / (2 sigma^2)) / sum, d = j - ksize // 2, in double in j
+    order, then rounded (host tensor [ksize]; `sigma` is taken at f32 precision, as the C-ABI receives it)."""
+    import math
+    s = float(torch.tensor(float(sigma), dtype=torch.float32))
+    w = [math.exp(-(float(j - ksize // 2) ** 2) / (2.0 * s * s)) for j in range(ksize)]
+    tot = 0.0
+    for v in w:
+        tot += v
+    return torch.tensor([v / tot for v in w], dtype=torch.float64).float()
+
+
+def perturb_clips(clip: torch.Tensor, rank: torch.Tensor, k: torch.Tensor, grid, layout: str, mode: str,
+                  base: torch.Tensor | None = None, out: torch.Tensor | None = None) -> torch.Tensor:
+    """The F perturbed copies of a clip batch in one launch (vc_perturb_clips).  clip f32 [B,T,C,H,W] (layout "btchw")
+    or [B,C,T,H,W] ("bcthw"); base the same shape, or None for 0.0; rank int32 [B, Tg*Hg*Wg], the position of every
+    cell of `grid` = (Tg, Hg, Wg) in the order of removal; k int32 [F].  Pixel (t, y, x) is in cell
+    ((t*Tg//T)*Hg + y*Hg//H)*Wg + x*Wg//W.  out f32 [F, *clip.shape]: mode "deletion" takes base where rank < k[f] and
+    the clip elsewhere, "insertion" the reverse; the values are copied bit for bit."""
+    opt = [t for t in (base, out) if t is not None]
+    _dev(clip, rank, k, *opt)
+    _need(layout in CLIP_LAYOUT, f"perturb_clips: layout must be one of {sorted(CLIP_LAYOUT)}")
+    _need(mode in PERTURB_MODE, f"perturb_clips: mode must be one of {sorted(PERTURB_MODE)}")
+    _need(clip.dtype == torch.float32 and clip.dim() == 5 and clip.is_contiguous(), "perturb_clips: clip f32 contiguous, 5-D")
+    B = clip.shape[0]
+    (T, C) = (clip.shape[1], clip.shape[2]) if layout == "btchw" else (clip.shape[2], clip.shape[1])
+    H, W = clip.shape[3], clip.shape[4]
+    _need(len(grid) == 3 and all(isinstance(g, int) and g > 0 for g in grid), "perturb_clips: grid = (Tg, Hg, Wg), positive ints")
+    Tg, Hg, Wg = grid
+    _need(Tg <= T and Hg <= H and Wg <= W, f"perturb_clips: grid {tuple(grid)} larger than the clip's {(T, H, W)}")
+    _need(rank.dtype == torch.int32 and rank.is_contiguous() and tuple(rank.shape) == (B, Tg * Hg * Wg),
+          "perturb_clips: rank int32 [B, Tg*Hg*Wg]")
+    _need(k.dtype == torch.int32 and k.is_contiguous() and k.dim() == 1 and k.numel() >= 1, "perturb_clips: k int32 [F]")
+    _need(base is None or (base.dtype == torch.float32 and base.is_contiguous() and base.shape == clip.shape),
+          "perturb_clips: base f32 contiguous, the clip's shape")
+    F = k.numel()
+    if out is None:
+        out = torch.empty((F,) + tuple(clip.shape), dtype=torch.float32, device=clip.device)
+    _need(out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (F,) + tuple(clip.shape),
+          "perturb_clips: out f32 contiguous [F, *clip.shape]")
+    _need(len({t.device for t in (clip, rank, k, out, *opt)}) == 1, "perturb_clips: all tensors on one device")
+    _lib.call("vc_perturb_clips", _p(clip), None if base is None else _p(base), _p(rank), _p(k), B, C, T, H, W,
+              CLIP_LAYOUT[layout], Tg, Hg, Wg, F, PERTURB_MODE[mode], _p(out), _stream(clip))
+    return out
+
+
+def gaussian_blur_planes(x: torch.Tensor, ksize: int = 11, sigma: float = 5.0, out: torch.Tensor | None = None,
+                         work: torch.Tensor | None = None) -> torch.Tensor:
+    """Separable Gaussian blur with replicated edges over the last two dimensions of x f32 [..., H, W]
+    (vc_gaussian_blur_planes; taps: gaussian_taps(ksize, sigma)); ksize odd and <= 31.  out / work: f32 buffers of
+    x's size (allocated when absent); x is left unchanged."""
+    opt = [t for t in (out, work) if t is not None]
+    _dev(x, *opt)
+    _need(x.dtype == torch.float32 and x.dim() >= 2 and x.is_contiguous() and x.numel() > 0,
+          "gaussian_blur_planes: x f32 contiguous [..., H, W], not empty")
+    _need(isinstance(ksize, int) and 1 <= ksize <= 31 and ksize % 2 == 1, "gaussian_blur_planes: ksize odd and <= 31")
+    _need(float(sigma) > 0 and float(sigma) != float("inf"), "gaussian_blur_planes: sigma must be positive and finite")
+    if out is None:
+        out = torch.empty_like(x)
+    if work is None:
+        work = torch.empty_like(x)
+    _need(out.dtype == torch.float32 and out.is_contiguous() and out.shape == x.shape,
+          "gaussian_blur_planes: out f32 contiguous, x's shape")
+    _need(work.dtype == torch.float32 and work.is_contiguous() and work.numel() >= x.numel(),
+          "gaussian_blur_planes: work f32 contiguous, at least x's size")
+    _need(len({t.device for t in (x, out, work)}) == 1, "gaussian_blur_planes: all tensors on one device")
+    H, W = x.shape[-2], x.shape[-1]
+    _lib.call("vc_gaussian_blur_planes", _p(x), x.numel() // (H * W), H, W, ksize, float(sigma), _p(out), _p(work),
+              _stream(x))
+    return out

@@ -989,6 +989,28 @@ int vc_frame_cam(const uint16_t* x, int64_t ldx, const float* g, int64_t ldg, in
 int vc_frame_avgpool_bwd(const float* g, int64_t ldg, int64_t N, int64_t P, int64_t C, uint16_t* out, int64_t ldo,
                          hipStream_t stream);
 
+/* ---- saliency faithfulness: the deletion / insertion games on a clip batch (perturb.hip; vclip_amd/faithfulness.py) ----
+ * clip f32, B clips in layout 0 [B,T,C,H,W] or 1 [B,C,T,H,W]; base (may be NULL: 0.0f everywhere) the same shape.
+ * rank int32 [B, Tg*Hg*Wg]: the position of every saliency cell in the order of removal; k int32 [F]: how many cells
+ * each of the F copies touches.  Pixel (t, y, x) of clip b belongs to cell c = ((t*Tg/T)*Hg + y*Hg/H)*Wg + x*Wg/W
+ * (integer division; any grid with Tg <= T, Hg <= H, Wg <= W, cells need not divide the clip).  out f32
+ * [F, B, <clip layout>]: mode 0 (deletion) out[f][b][.] = rank[b][c] < k[f] ? base : clip; mode 1 (insertion) the
+ * reverse.  A pure select (the output bits are the inputs'), one launch, one read of clip, base and rank.  16-byte
+ * accesses when B*T*C*H*W % 4 == 0 and clip, base and out are 16-byte aligned, 4-byte ones otherwise.  Fewer than 2^31
+ * elements per copy.  out may alias no input. */
+int vc_perturb_clips(const float* clip, const float* base, const int32_t* rank, const int32_t* k, int64_t B, int64_t C,
+                     int64_t T, int64_t H, int64_t W, int layout, int64_t Tg, int64_t Hg, int64_t Wg, int64_t F, int mode,
+                     float* out, hipStream_t stream);
+
+/* Separable Gaussian blur of `planes` f32 planes [H, W] with replicated edges: ksize odd and <= 31 taps
+ * exp(-d^2 / (2 sigma^2)) / sum, d = j - ksize/2, computed on the host in double in j order and rounded to f32; rows
+ * first (in -> work), then columns (work -> out), each output x_c + sum_j w_j (x_j - x_c) around its centre pixel x_c,
+ * one fmaf per tap in j order from 0.0f (a constant plane comes back exactly): deterministic, and plane p's output does
+ * not depend on `planes`.  H and W may be smaller than ksize/2.  work f32 [planes*H*W]; in, out
+ * and work may not alias one another. */
+int vc_gaussian_blur_planes(const float* in, int64_t planes, int64_t H, int64_t W, int64_t ksize, float sigma, float* out,
+                            float* work, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -56,6 +56,14 @@ times VideoResNet50LSTM.explain: ResNet50-LSTM (hidden 256, two layers), 32 x 22
 the same process; bptt_ms (the head's and the recurrence's backward with the two lstm_dx GEMMs and the P = 1 vc_frame_cam,
 alone, on what explain kept), for res4 chain_ms (the backbone's data-gradient chain alone), the bytes of the kept backbone
 activations, and forward_after_ms.
+
+  python tools/saliency_time.py --family <any of the five> --check [--out profiles/saliency_check_<family>.json]
+
+times the perturbation test that scores such a map (vclip_amd.faithfulness) at the same full sizes, B = 1, the same medians:
+forward_ms (`model(clip)`), explain_ms (rollout, or Grad-CAM at res5), faithfulness_zero_ms and faithfulness_blur_ms
+(faithfulness(steps=10): 33 forwards, three ops.perturb_clips launches, host ranks and scores; with the blurred baseline
+also three blurs), perturb_ms (the one launch that writes the 11 clips, with the bytes it moves) and blur_ms (the two
+launches of ops.gaussian_blur_planes), and forward_after_ms.
 """
 from __future__ import annotations
 
@@ -324,20 +332,98 @@ def lstm(a) -> dict:
             "device": torch.cuda.get_device_name(0), "batches": {str(B): r}}
 
 
+def check(a) -> dict:
+    """--check: the perturbation test of vclip_amd.faithfulness at the family's full size, B = 1, against the plain forward
+    and explain of the same process: faithfulness(steps=10) with both baselines, and its two kernels alone"""
+    from vclip_amd import ops
+    from vclip_amd.build import source_hash
+    from vclip_amd.faithfulness import BLUR_KSIZE, BLUR_SIGMA, cell_ranks, faithfulness, step_counts
+    from vclip_amd.weights import make_synthetic_clips, make_synthetic_video
+
+    steps, B = 10, 1
+    if a.family == "vivit":
+        from vclip_amd.vivit import create_model
+        name, model, how = "ViViT-B/16x2 32 x 224^2", create_model(num_frames=32, device=DEV), dict(method="rollout")
+        clip = make_synthetic_clips(B, 32, 224, seed=1)
+    elif a.family == "timesformer":
+        from vclip_amd.timesformer import create_model
+        name, model, how = "TimeSformer-B 8 x 224^2", create_model(num_frames=8, device=DEV), dict(method="rollout")
+        clip = make_synthetic_clips(B, 8, 224, seed=1)
+    elif a.family == "swin":
+        from vclip_amd.swin3d import create_model
+        name, model, how = "Swin-T 32 x 224^2", create_model(None, "tiny", num_classes=2, device=DEV), dict(method="rollout")
+        clip = make_synthetic_video(B, 32, 224, seed=1)
+    elif a.family == "resnet3d":
+        from vclip_amd.resnet3d import create_model
+        name, model, how = "ResNet3D-50 32 x 224^2", create_model(None, device=DEV), dict(method="gradcam", layer="res5")
+        clip = make_synthetic_video(B, 32, 224, seed=1)
+    else:
+        from vclip_amd.resnet50_lstm import create_model
+        name, model, how = "ResNet50-LSTM 32 x 224^2", create_model(device=DEV), dict(method="gradcam", layer="res5")
+        clip = make_synthetic_video(B, 32, 224, seed=1)
+    model = model.eval()
+    clip = torch.from_numpy(clip).to(DEV)
+    layout = "btchw" if a.family in ("vivit", "timesformer") else "bcthw"
+
+    def forward():
+        model(pixel_values=clip) if layout == "btchw" else model(clip)
+
+    def explain():
+        return model.explain(clip, **how)
+
+    r = {"forward_ms": _median(forward, a.reps, a.warmup), "explain": how, "explain_ms": _median(explain, a.reps, a.warmup)}
+    ex = explain()
+    grid = tuple(ex.saliency.shape[1:])
+    for baseline in ("zero", "blur"):
+        def faith():
+            faithfulness(model, clip, ex, steps=steps, baseline=baseline)
+
+        r[f"faithfulness_{baseline}_ms"] = _median(faith, a.reps, a.warmup)
+    rank = cell_ranks(ex.saliency).to(DEV)
+    k = torch.tensor(step_counts(rank.shape[1], steps), dtype=torch.int32, device=DEV)
+    out, blurred, work = torch.empty((steps + 1,) + tuple(clip.shape), device=DEV), torch.empty_like(clip), torch.empty_like(clip)
+
+    def perturb():
+        ops.perturb_clips(clip, rank, k, grid, layout, "deletion", out=out)
+
+    def blur():
+        ops.gaussian_blur_planes(clip, BLUR_KSIZE, BLUR_SIGMA, out=blurred, work=work)
+
+    r["perturb_ms"], r["blur_ms"] = _median(perturb, a.reps, a.warmup), _median(blur, a.reps, a.warmup)
+    r["forward_after_ms"] = _median(forward, a.reps, a.warmup)
+    r["steps"], r["grid"], r["forwards"] = steps, list(grid), 3 * (steps + 1)
+    r["perturb_bytes"] = clip.numel() * 4 * (steps + 2) + rank.numel() * 4  # one read of the clip, steps + 1 writes
+    r["perturb_gb_per_s"] = r["perturb_bytes"] / (r["perturb_ms"] * 1e-3) / 1e9
+    r["blur_bytes"] = clip.numel() * 4 * 4  # rows: read + write, columns: read + write
+    r["blur_gb_per_s"] = r["blur_bytes"] / (r["blur_ms"] * 1e-3) / 1e9
+    r["faithfulness_over_forward"] = r["faithfulness_zero_ms"] / r["forward_ms"]
+    r["faithfulness_over_explain"] = r["faithfulness_zero_ms"] / r["explain_ms"]
+    print(f"{name} B = {B}: forward {r['forward_ms']:.3f} ms (after {r['forward_after_ms']:.3f}), explain({how}) "
+          f"{r['explain_ms']:.3f} ms, faithfulness(steps={steps}) {r['faithfulness_zero_ms']:.2f} ms "
+          f"({r['faithfulness_over_forward']:.1f} forwards' time for {r['forwards']} forwards), with the blurred baseline "
+          f"{r['faithfulness_blur_ms']:.2f} ms; perturb_clips alone {r['perturb_ms']:.3f} ms "
+          f"({r['perturb_gb_per_s']:.0f} GB/s), gaussian_blur_planes alone {r['blur_ms']:.3f} ms "
+          f"({r['blur_gb_per_s']:.0f} GB/s)", flush=True)
+    return {"model": name, "reps": a.reps, "warmup": a.warmup, "build": source_hash(),
+            "device": torch.cuda.get_device_name(0), "batches": {str(B): r}}
+
+
 def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--family", choices=("vivit", "timesformer", "swin", "resnet3d", "lstm"), default="vivit")
+    ap.add_argument("--check", action="store_true", help="time the perturbation test (vclip_amd.faithfulness) instead")
     ap.add_argument("--out", default=None)
     ap.add_argument("--reps", type=int, default=15)
     ap.add_argument("--warmup", type=int, default=3)
     a = ap.parse_args()
     if a.out is None:
-        a.out = os.path.join(ROOT, "profiles", "saliency_time.json" if a.family == "vivit" else
-                             f"saliency_time_{a.family}.json")
+        a.out = os.path.join(ROOT, "profiles", f"saliency_check_{a.family}.json" if a.check else
+                             "saliency_time.json" if a.family == "vivit" else f"saliency_time_{a.family}.json")
     if not torch.cuda.is_available():
         raise SystemExit("saliency_time.py needs a GPU")
-    if a.family in ("timesformer", "swin", "resnet3d", "lstm"):
-        res = {"timesformer": timesformer, "swin": swin, "resnet3d": resnet3d, "lstm": lstm}[a.family](a)
+    if a.check or a.family in ("timesformer", "swin", "resnet3d", "lstm"):
+        legs = {"timesformer": timesformer, "swin": swin, "resnet3d": resnet3d, "lstm": lstm}
+        res = check(a) if a.check else legs[a.family](a)
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:
             json.dump(res, f, indent=1)
