@@ -94,6 +94,11 @@ SIGNATURES = {
     "vc_perturb_clips": ([c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_int, c_i64, c_i64, c_i64, c_i64, c_int,
                           c_p, c_p], c_int),
     "vc_gaussian_blur_planes": ([c_p, c_i64, c_i64, c_i64, c_i64, c_f, c_p, c_p, c_p], c_int),
+    # RISE saliency (csrc/rise.hip)
+    "vc_rise_mask_tile": ([], c_int),
+    "vc_rise_apply": ([c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_int, c_i64, c_i64, c_i64, c_i64, c_p, c_p],
+                      c_int),
+    "vc_rise_accumulate": ([c_p, c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_p, c_p], c_int),
     "vc_maxpool3d_bwd": ([c_p, c_i64, c_p, c_int, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_p, c_p, c_p, c_p, c_i64,
                           c_p], c_int),
     "vc_batchnorm_train_fwd": ([c_p, c_i64, c_i64, c_i64, c_p, c_p, c_f, c_f, c_p, c_p, c_p, c_int, c_i64, c_int, c_p,

@@ -248,8 +248,13 @@ SALIENCY_CHECK_HELP = (
     "as the map's cells are deleted from the clip and inserted into a zero clip in the map's order, and deleted in a "
     "random order.  The result JSON's \"saliency\" object gains a \"faithfulness\" object with the three curves and "
     "their areas (deletion_gain = random_deletion_auc - deletion_auc: positive when the map beats chance).")
+RISE_SALIENCY_HELP = (
+    "  rise: RISE (Petsiuk et al. 2018), the class-specific black-box map at pixel resolution (vclip_amd.rise_map): the "
+    "score-weighted mean of --rise_masks smooth random masks, for --saliency_class; <video>_saliency.npy is then f32 "
+    "[T, H, W] and the \"saliency\" object names masks, cells, keep and seed.")
 # per family: the --saliency methods that take --saliency_class
-CLASS_SPECIFIC_SALIENCY = {"vivit": ("grad_rollout",), "resnet3d": ("gradcam", "hirescam")}
+CLASS_SPECIFIC_SALIENCY = {"vivit": ("grad_rollout", "rise"), "timesformer": ("rise",), "swin": ("rise",),
+                           "resnet3d": ("gradcam", "hirescam", "rise")}
 
 
 def _positive_int(text: str) -> int:
@@ -260,12 +265,18 @@ def _positive_int(text: str) -> int:
 
 
 class _SaliencyCheckParser(argparse.ArgumentParser):
-    """The inference parser as run_inference builds it: --saliency_check without --saliency is an error"""
+    """The inference parser as run_inference builds it: --saliency_check without --saliency is an error, and so is
+    TimeSformer's and Swin's --saliency_class with a method that is not class-specific (`class_methods`, set by
+    build_parser for those two; ViViT's and ResNet3D's is checked by run_inference, as before)"""
+    class_methods = None
 
     def parse_args(self, args=None, namespace=None):
         a = super().parse_args(args, namespace)
         if getattr(a, "saliency_check", None) is not None and getattr(a, "saliency", None) is None:
             self.error("--saliency_check needs --saliency")
+        if (self.class_methods is not None and getattr(a, "saliency_class", None) is not None
+                and getattr(a, "saliency", None) not in self.class_methods):
+            self.error(f"--saliency_class needs --saliency {' or '.join(self.class_methods)}")
         return a
 
 
@@ -283,8 +294,9 @@ def _temporal_patch(model) -> int:
 def build_parser(fam: Family, inference: bool, saliency: bool = False):
     """The folder's reference flags (plus ViViT's --saliency / --saliency_class).  saliency=True, as run_inference
     builds it: the TimeSformer, Swin and ResNet3D inference parsers also get their own --saliency (ResNet3D's with
-    --saliency_class and --saliency_layer); the two-argument form keeps the flag surface those families had before
-    their `explain` existed."""
+    --saliency_class and --saliency_layer), and all four the method `rise` with --rise_masks and --rise_seed (and
+    TimeSformer and Swin the --saliency_class that only `rise` takes); the two-argument form keeps the flag surface
+    those families had before their `explain` existed."""
     if fam.name == "lstm":
         return build_parser_lstm(inference)
     cls = _SaliencyCheckParser if inference and saliency else argparse.ArgumentParser
@@ -303,22 +315,27 @@ def build_parser(fam: Family, inference: bool, saliency: bool = False):
             p.add_argument("--save_viz", action="store_true")
         else:
             p.add_argument("--visualize", action="store_true")
+        rise = ["rise"] if saliency else []
+        more = RISE_SALIENCY_HELP if saliency else ""
         if fam.name == "vivit":
             # not in the reference, whose HF model can return its attentions: which tubelets produced the label
-            p.add_argument("--saliency", type=str, default=None, choices=["rollout", "cls_attention", "grad_rollout"],
-                           help=VIVIT_SALIENCY_HELP)
+            p.add_argument("--saliency", type=str, default=None,
+                           choices=["rollout", "cls_attention", "grad_rollout"] + rise, help=VIVIT_SALIENCY_HELP + more)
             p.add_argument("--saliency_class", type=int, default=None,
                            help="with --saliency grad_rollout: the class index whose evidence is mapped (absent: the "
                                 "predicted class); the result JSON's \"saliency\" object names it as target_class / "
                                 "target_label")
-        elif fam.name == "timesformer" and saliency:
-            p.add_argument("--saliency", type=str, default=None, choices=["rollout", "cls_attention"],
-                           help=TIMESFORMER_SALIENCY_HELP)
-        elif fam.name == "swin" and saliency:
-            p.add_argument("--saliency", type=str, default=None, choices=["rollout"], help=SWIN_SALIENCY_HELP)
+        elif fam.name in ("timesformer", "swin") and saliency:
+            own = ["rollout", "cls_attention"] if fam.name == "timesformer" else ["rollout"]
+            p.add_argument("--saliency", type=str, default=None, choices=own + rise,
+                           help=(TIMESFORMER_SALIENCY_HELP if fam.name == "timesformer" else SWIN_SALIENCY_HELP) + more)
+            p.add_argument("--saliency_class", type=int, default=None,
+                           help="with --saliency rise: the class index whose evidence is mapped (absent: the predicted "
+                                "class); the result JSON's \"saliency\" object names it as target_class / target_label")
+            p.class_methods = CLASS_SPECIFIC_SALIENCY[fam.name]
         elif fam.name == "resnet3d" and saliency:
-            p.add_argument("--saliency", type=str, default=None, choices=["gradcam", "hirescam"],
-                           help=RESNET3D_SALIENCY_HELP)
+            p.add_argument("--saliency", type=str, default=None, choices=["gradcam", "hirescam"] + rise,
+                           help=RESNET3D_SALIENCY_HELP + more)
             p.add_argument("--saliency_class", type=int, default=None,
                            help="with --saliency: the class index whose evidence is mapped (absent: the predicted "
                                 "class); the result JSON's \"saliency\" object names it as target_class / target_label")
@@ -326,6 +343,9 @@ def build_parser(fam: Family, inference: bool, saliency: bool = False):
                            help="with --saliency: the stage whose output is explained (res4: twice the spatial "
                                 "resolution, through the res5 data-gradient chain)")
         if saliency:
+            p.add_argument("--rise_masks", type=_positive_int, default=4000, metavar="N",
+                           help="with --saliency rise: the number of random masks, one forward each (4000: the paper's)")
+            p.add_argument("--rise_seed", type=int, default=0, help="with --saliency rise: the seed of the mask sampler")
             p.add_argument("--saliency_check", type=_positive_int, default=None, metavar="STEPS",
                            help=SALIENCY_CHECK_HELP)
         return p
@@ -621,7 +641,11 @@ def run_inference(fam_name, argv=None):
     out.mkdir(parents=True, exist_ok=True)
     if saliency:
         # the label above is the ordinary forward's, the same with and without the flag; the map is explain's
-        if fam.name == "resnet3d":
+        if saliency == "rise":  # black box: the same call for every family, the asked class or the label printed above
+            from .rise import rise_map
+            ex = rise_map(model, x, target=pred if saliency_class is None else saliency_class, masks=args.rise_masks,
+                          seed=args.rise_seed)
+        elif fam.name == "resnet3d":
             ex = model.explain(x, method=saliency, target=pred if saliency_class is None else saliency_class,
                                layer=args.saliency_layer)
         elif saliency == "grad_rollout":  # class-specific: the asked class, or the label printed above
@@ -629,7 +653,7 @@ def run_inference(fam_name, argv=None):
         else:
             ex = model.explain(x, method=saliency)
         sal = ex.saliency[0].numpy()
-        kt = _temporal_patch(model)
+        kt = 1 if saliency == "rise" else _temporal_patch(model)  # RISE's map is per sampled frame
         npy = f"{Path(args.video_path).stem}_saliency.npy"
         np.save(out / npy, sal)
         res["saliency"] = {"method": saliency, "file": npy, "shape": list(sal.shape),
@@ -637,7 +661,9 @@ def run_inference(fam_name, argv=None):
                            "tubelet_frame_indices": [frame_idx[i:i + kt] for i in range(0, len(frame_idx), kt)]}
         if ex.target is not None:
             res["saliency"].update(target_class=ex.target[0], target_label=id2label[ex.target[0]])
-        if fam.name == "resnet3d":
+        if saliency == "rise":
+            res["saliency"].update(masks=ex.masks, cells=list(ex.cells), keep=ex.keep, seed=ex.seed)
+        elif fam.name == "resnet3d":
             res["saliency"]["layer"] = args.saliency_layer
             if not sal.any():  # the map has nothing positive: no evidence for the class at this layer
                 res["saliency"]["empty"] = True

@@ -1776,3 +1776,66 @@ def gaussian_blur_planes(x: torch.Tensor, ksize: int = 11, sigma: float = 5.0, o
     _lib.call("vc_gaussian_blur_planes", _p(x), x.numel() // (H * W), H, W, ksize, float(sigma), _p(out), _p(work),
               _stream(x))
     return out
+
+
+# ---- RISE saliency (csrc/rise.hip; vclip_amd/rise.py) ----
+def rise_mask_tile() -> int:
+    """The most masks vc_rise_apply / vc_rise_accumulate stage in LDS per round (no result depends on it)."""
+    return int(_lib.load().vc_rise_mask_tile())
+
+
+def _rise_masks(name: str, bits: torch.Tensor, shifts: torch.Tensor, cells, T: int, H: int, W: int) -> int:
+    """checks cells, bits uint8 [F, ct+2, ch+2, cw+2] and shifts int32 [F, 3] against the extent; returns F"""
+    _need(len(cells) == 3 and all(isinstance(c, int) and not isinstance(c, bool) and c > 0 for c in cells),
+          f"{name}: cells = (ct, ch, cw), positive ints")
+    ct, ch, cw = cells
+    _need(ct <= T and ch <= H and cw <= W, f"{name}: cells {tuple(cells)} larger than the clip's {(T, H, W)}")
+    _need(bits.dtype == torch.uint8 and bits.is_contiguous() and bits.dim() == 4 and bits.shape[0] >= 1 and
+          tuple(bits.shape[1:]) == (ct + 2, ch + 2, cw + 2), f"{name}: bits uint8 contiguous [F, ct+2, ch+2, cw+2]")
+    F = bits.shape[0]
+    _need(shifts.dtype == torch.int32 and shifts.is_contiguous() and tuple(shifts.shape) == (F, 3),
+          f"{name}: shifts int32 contiguous [F, 3]")
+    return F
+
+
+def rise_apply(clip: torch.Tensor, bits: torch.Tensor, shifts: torch.Tensor, cells, layout: str,
+               base: torch.Tensor | None = None, out: torch.Tensor | None = None) -> torch.Tensor:
+    """The clip batch under F RISE masks in one launch (vc_rise_apply).  clip f32 [B,T,C,H,W] (layout "btchw") or
+    [B,C,T,H,W] ("bcthw"); base the same shape, or None for 0.0; bits uint8 [F, ct+2, ch+2, cw+2] and shifts int32
+    [F, 3] as vclip_amd.rise.rise_masks draws them for `cells` = (ct, ch, cw) (every shift must lie in [0, S): the
+    kernel does not check the values).  out f32 [F, *clip.shape] = fmaf(m, clip, (1 - m) * base), m the mask's
+    trilinear interpolation at the pixel, the same for every clip and channel."""
+    opt = [t for t in (base, out) if t is not None]
+    _dev(clip, bits, shifts, *opt)
+    _need(layout in CLIP_LAYOUT, f"rise_apply: layout must be one of {sorted(CLIP_LAYOUT)}")
+    _need(clip.dtype == torch.float32 and clip.dim() == 5 and clip.is_contiguous(), "rise_apply: clip f32 contiguous, 5-D")
+    B = clip.shape[0]
+    (T, C) = (clip.shape[1], clip.shape[2]) if layout == "btchw" else (clip.shape[2], clip.shape[1])
+    H, W = clip.shape[3], clip.shape[4]
+    F = _rise_masks("rise_apply", bits, shifts, cells, T, H, W)
+    _need(base is None or (base.dtype == torch.float32 and base.is_contiguous() and base.shape == clip.shape),
+          "rise_apply: base f32 contiguous, the clip's shape")
+    if out is None:
+        out = torch.empty((F,) + tuple(clip.shape), dtype=torch.float32, device=clip.device)
+    _need(out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (F,) + tuple(clip.shape),
+          "rise_apply: out f32 contiguous [F, *clip.shape]")
+    _need(len({t.device for t in (clip, bits, shifts, out, *opt)}) == 1, "rise_apply: all tensors on one device")
+    _lib.call("vc_rise_apply", _p(clip), None if base is None else _p(base), _p(bits), _p(shifts), B, C, T, H, W,
+              CLIP_LAYOUT[layout], cells[0], cells[1], cells[2], F, _p(out), _stream(clip))
+    return out
+
+
+def rise_accumulate(acc: torch.Tensor, bits: torch.Tensor, shifts: torch.Tensor, w: torch.Tensor, cells) -> torch.Tensor:
+    """acc f32 [B, T, H, W] += sum over the F masks, in index order, of w[f][b] * m_f, one fmaf per mask
+    (vc_rise_accumulate; in place, returns acc).  w f32 [F, B]; bits, shifts and cells as rise_apply takes them.  Any
+    split of the masks into consecutive calls gives the same bits as one call."""
+    _dev(acc, bits, shifts, w)
+    _need(acc.dtype == torch.float32 and acc.dim() == 4 and acc.is_contiguous() and acc.numel() > 0,
+          "rise_accumulate: acc f32 contiguous [B, T, H, W]")
+    B, T, H, W = acc.shape
+    F = _rise_masks("rise_accumulate", bits, shifts, cells, T, H, W)
+    _need(w.dtype == torch.float32 and w.is_contiguous() and tuple(w.shape) == (F, B), "rise_accumulate: w f32 contiguous [F, B]")
+    _need(len({t.device for t in (acc, bits, shifts, w)}) == 1, "rise_accumulate: all tensors on one device")
+    _lib.call("vc_rise_accumulate", _p(bits), _p(shifts), _p(w), B, T, H, W, cells[0], cells[1], cells[2], F, _p(acc),
+              _stream(acc))
+    return acc

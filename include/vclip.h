@@ -1011,6 +1011,32 @@ int vc_perturb_clips(const float* clip, const float* base, const int32_t* rank, 
 int vc_gaussian_blur_planes(const float* in, int64_t planes, int64_t H, int64_t W, int64_t ksize, float sigma, float* out,
                             float* work, hipStream_t stream);
 
+/* ---- RISE saliency: smooth random masks on a clip batch and their weighted sum (rise.hip; vclip_amd/rise.py) ----
+ * F masks over the clip extent (T, H, W), cells (ct, ch, cw) with 1 <= c <= extent, cell sizes St = ceil(T/ct), Sh, Sw.
+ * bits uint8 [F, ct+2, ch+2, cw+2] (0 or 1), shifts int32 [F, 3] = (dt, dy, dx) with 0 <= d < S.  For pixel (t, y, x):
+ * u = t + dt, i = u / St, ft = float(u % St) / float(St) (one IEEE division); (j, fy) and (k, fx) likewise;
+ * m_f(t, y, x) = the trilinear interpolation of bits[f][i..i+1][j..j+1][k..k+1], along x, then y, then t, each step
+ * fmaf(fr, b - a, a).  Equal corner bits give that bit exactly.  The bit grids are staged in LDS: (ct+2)*(ch+2)*(cw+2)
+ * may not exceed 4096, and the masks go through it in rounds of at most vc_rise_mask_tile(); no result depends on
+ * the rounds.  The fractions come from an LDS table of St + Sh + Sw entries, which may not exceed 4096. */
+int vc_rise_mask_tile(void);
+
+/* clip f32, B clips in layout 0 [B,T,C,H,W] or 1 [B,C,T,H,W]; base (may be NULL: 0.0f everywhere) the same shape; every
+ * clip and channel sees the same masks.  out f32 [F, B, <clip layout>] = fmaf(m, clip, (1 - m) * base), or m * clip
+ * without a base: m == 1 gives the clip's value and m == 0 the base's exactly (finite inputs).  One launch, one read of
+ * clip and base.  16-byte accesses when B*T*C*H*W % 4 == 0 and clip, base and out are 16-byte aligned, 4-byte ones
+ * otherwise.  Fewer than 2^31 elements per copy.  out may alias no input. */
+int vc_rise_apply(const float* clip, const float* base, const uint8_t* bits, const int32_t* shifts, int64_t B, int64_t C,
+                  int64_t T, int64_t H, int64_t W, int layout, int64_t ct, int64_t ch, int64_t cw, int64_t F, float* out,
+                  hipStream_t stream);
+
+/* acc f32 [B, T, H, W], in place, w f32 [F, B]: per pixel a = acc; for f = 0..F-1: a = fmaf(w[f][b], m_f(t, y, x), a);
+ * acc = a.  The masks are taken in index order and nothing is atomic: F masks in one call or split into consecutive
+ * calls give the same bits, as do two runs, and clip b's result does not depend on B.  Fewer than 2^31 pixels and
+ * weights.  acc may alias no input. */
+int vc_rise_accumulate(const uint8_t* bits, const int32_t* shifts, const float* w, int64_t B, int64_t T, int64_t H,
+                       int64_t W, int64_t ct, int64_t ch, int64_t cw, int64_t F, float* acc, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
