@@ -11,7 +11,7 @@ PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 REPO_ROOT = os.path.dirname(PKG_DIR)
 
 __all__ = ["PKG_DIR", "REPO_ROOT", "faithfulness", "perturbation_curve", "PerturbationCurve", "rise_map",
-           "RiseExplanation"]
+           "RiseExplanation", "lora"]
 
 
 def __getattr__(name):
@@ -24,4 +24,7 @@ def __getattr__(name):
     if name in ("rise_map", "RiseExplanation"):
         import importlib
         return getattr(importlib.import_module(".rise", __name__), name)
+    if name == "lora":  # LoRA fine-tuning of ViViT (vclip_amd/lora.py)
+        import importlib
+        return importlib.import_module(".lora", __name__)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

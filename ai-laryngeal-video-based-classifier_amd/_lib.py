@@ -143,6 +143,11 @@ SIGNATURES = {
     "vc_adamw_tab": ([c_p, c_p, c_p, c_p, c_i64, c_f, c_f, c_f, c_f, c_f, c_p, c_p, c_i64, c_f, c_p], c_int),
     "vc_adamw_step_tick": ([c_p, c_p], c_int),
     "vc_pack_weight": ([c_p, c_i64, c_i64, c_i64, c_f, c_p, c_p, c_p], c_int),
+    # LoRA fine-tuning (csrc/lora.hip)
+    "vc_lora_merge": ([c_p, c_i64, c_i64, c_i64, c_i64, c_p, c_p, c_i64, c_f, c_i64, c_f, c_p, c_i64, c_p, c_i64, c_p,
+                       c_i64, c_p], c_int),
+    "vc_lora_down": ([c_p, c_i64, c_i64, c_i64, c_p, c_i64, c_i64, c_i64, c_p, c_p], c_int),
+    "vc_lora_wgrad": ([c_p, c_i64, c_p, c_i64, c_i64, c_i64, c_f, c_int, c_p, c_p, c_i64, c_p], c_int),
     # TimeSformer train step
     "vc_temporal_attention_bwd": ([c_p, c_i64, c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_p, c_i64, c_p], c_int),
     "vc_gelu_erf": ([c_p, c_i64, c_i64, c_i64, c_p, c_i64, c_p], c_int),

@@ -380,6 +380,16 @@ def build_parser(fam: Family, inference: bool, saliency: bool = False):
     p.add_argument("--checkpoint_path", type=str, default=None)
     if fam.name == "resnet3d":
         p.add_argument("--weighted_sampling", action="store_true")
+    if fam.name == "vivit":
+        # not in the reference: LoRA fine-tuning (vclip_amd/lora.py) -- the base frozen, rank-R adapters trained
+        p.add_argument("--lora_rank", type=int, default=0, metavar="R",
+                       help="train rank-R LoRA adapters (and the classifier) on a frozen base instead of every weight "
+                            "(0: off); the checkpoint's model_state_dict has them folded in")
+        p.add_argument("--lora_alpha", type=float, default=None, metavar="A", help="LoRA scale alpha (absent: 2R)")
+        p.add_argument("--lora_targets", type=str, default="q,v",
+                       help="comma-separated projections that get adapters, out of q,k,v,o,fc1,fc2")
+        p.add_argument("--lora_layers", type=int, default=0, metavar="N",
+                       help="adapters on the last N encoder layers only (0: all)")
     return p
 
 
@@ -494,6 +504,13 @@ def run_main(fam_name, argv=None):
     model = fam.create_model(args, class_labels, device, logger)
     if args.checkpoint_path:
         _load_weights(model, args.checkpoint_path, logger, fam)
+    use_lora = fam.name == "vivit" and getattr(args, "lora_rank", 0) > 0 and not args.skip_train
+    if use_lora:
+        from . import lora
+        lora.attach(model, rank=args.lora_rank, alpha=2.0 * args.lora_rank if args.lora_alpha is None else args.lora_alpha,
+                    targets=args.lora_targets, layers=args.lora_layers or None, seed=args.seed)
+        logger.info(f"LoRA: {lora.state_dict(model)['lora_config']}, {lora.trainable_parameters(model)} trainable "
+                    f"parameters")
     history = {"train_loss": [], "train_acc": [], "val_loss": [], "val_acc": []}
     if not args.skip_train:
         from .optim import AdamW
@@ -556,6 +573,10 @@ def run_main(fam_name, argv=None):
                                "label2id": model.config.label2id, "num_frames": args.num_frames,
                                "train_sampling": args.train_sampling, "val_sampling": args.val_sampling,
                                "test_sampling": args.test_sampling})
+                if use_lora:  # the adapters folded in: inference.py and --checkpoint_path read it as any checkpoint
+                    ck["model_state_dict"] = lora.merged_state_dict(model)
+                    ck["lora_state_dict"] = lora.state_dict(model)
+                    ck["lora_config"] = ck["lora_state_dict"]["lora_config"]
                 # (Swin3D: videoswintransformer/.../trainers/trainer.py:191-198 saves the six keys above)
                 torch.save(ck, path)
 
@@ -567,6 +588,8 @@ def run_main(fam_name, argv=None):
             if stopper.early_stop:
                 logger.info("Early stopping triggered")
                 break
+        if use_lora:
+            lora.detach(model)  # the best checkpoint's weights already hold its adapters
         _load_weights(model, best_path, logger, fam)
     m = evaluate(fam, model, loaders["test"], args, device, class_labels, exp.get_experiment_dir(),
                  args.test_sampling, logger)

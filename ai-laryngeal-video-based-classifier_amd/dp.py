@@ -22,6 +22,9 @@ import torch.distributed as dist
 
 class GradAllReduce:
     def __init__(self, model, group=None, bucket_bytes: int = 32 << 20, average: bool = True):
+        if getattr(model, "_lora", None) is not None:
+            raise NotImplementedError("dp.GradAllReduce is not supported with LoRA adapters attached; "
+                                      "lora.merge(model) first")
         self.model = model
         self.group = group
         self.world = dist.get_world_size(group)

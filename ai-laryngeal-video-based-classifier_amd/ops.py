@@ -1271,6 +1271,122 @@ def pack_weight(src: torch.Tensor, dst: torch.Tensor | None = None, dst_t: torch
               _p(dst_t) if dst_t is not None else None, _stream(src))
 
 
+# ---- LoRA fine-tuning (csrc/lora.hip) ----------------------------------------------------------
+LORA_MAX_RANK = 64  # csrc/lora.hip MAX_RANK
+
+
+def _lora_ab(name: str, a: torch.Tensor, b: torch.Tensor, N: int, K: int) -> int:
+    r = a.shape[0] if a.dim() == 2 else 0
+    _need(a.dtype == torch.float32 and b.dtype == torch.float32 and a.is_contiguous() and b.is_contiguous() and
+          1 <= r <= LORA_MAX_RANK and tuple(a.shape) == (r, K) and tuple(b.shape) == (N, r),
+          f"{name}: A f32 [r, {K}], B f32 [{N}, r] contiguous, 1 <= r <= {LORA_MAX_RANK}")
+    return r
+
+
+def lora_merge(w: torch.Tensor, a: torch.Tensor, b: torch.Tensor, s: float, dst: torch.Tensor | None = None,
+               dst_t: torch.Tensor | None = None, out: torch.Tensor | None = None, row0: int = 0,
+               nscaled: int = 0, scale: float = 1.0):
+    """Rows [row0, row0 + N) of v = w + s * b @ a in fp32 (w f32 [R, K], a f32 [r, K], b f32 [N, r]) into any of
+    dst bf16 [R, K], dst_t bf16 [K, R] and out f32 [R, K]; the other rows of the outputs are left alone.  Rows
+    < nscaled of the bf16 outputs are multiplied by scale, as pack_weight does."""
+    _dev(w, a, b)
+    _need(w.dtype == torch.float32 and w.dim() == 2 and w.stride(1) == 1, "lora_merge w f32 [R, K]")
+    R, K = w.shape
+    N = b.shape[0]
+    r = _lora_ab("lora_merge", a, b, N, K)
+    _need(0 <= row0 and row0 + N <= R, "lora_merge: rows [row0, row0 + N) outside w")
+    _need(dst is not None or dst_t is not None or out is not None, "lora_merge: no output")
+    if dst is not None:
+        _dev(dst)
+        _need(dst.dtype == torch.bfloat16 and dst.stride(1) == 1 and tuple(dst.shape) == (R, K), "lora_merge dst")
+    if dst_t is not None:
+        _dev(dst_t)
+        _need(dst_t.dtype == torch.bfloat16 and dst_t.stride(1) == 1 and tuple(dst_t.shape) == (K, R), "lora_merge dst_t")
+    if out is not None:
+        _dev(out)
+        _need(out.dtype == torch.float32 and out.stride(1) == 1 and tuple(out.shape) == (R, K) and
+              out.untyped_storage().data_ptr() != w.untyped_storage().data_ptr(), "lora_merge out (f32 [R, K], not w)")
+    _lib.call("vc_lora_merge", _p(w), w.stride(0), row0, N, K, _p(a), _p(b), r, s, nscaled, scale,
+              _p(dst) if dst is not None else None, dst.stride(0) if dst is not None else 0,
+              _p(dst_t) if dst_t is not None else None, dst_t.stride(0) if dst_t is not None else 0,
+              _p(out) if out is not None else None, out.stride(0) if out is not None else 0, _stream(w))
+
+
+def lora_down(x: torch.Tensor, s: torch.Tensor, out: torch.Tensor, transposed: bool = False,
+              m: int | None = None) -> torch.Tensor:
+    """out[m, j] = bf16(sum_k x[m, k] bf16(S[j, k])): x bf16 [M, K] (unit column stride, K % 32 == 0), S = s f32
+    [r, K], or with transposed=True s f32 [K, r] read as its transpose (the B of an adapter against dy); out bf16
+    [M, r]."""
+    _dev(x, s, out)
+    M = x.shape[0] if m is None else m
+    K = x.shape[1]
+    _need(x.dtype == torch.bfloat16 and x.dim() == 2 and x.stride(1) == 1 and x.shape[0] >= M, "lora_down x bf16 [M, K]")
+    _need(s.dtype == torch.float32 and s.dim() == 2 and s.is_contiguous() and
+          s.shape[0 if transposed else 1] == K, "lora_down s f32 [r, K] (or [K, r] transposed)")
+    r = s.shape[1 if transposed else 0]
+    _need(1 <= r <= LORA_MAX_RANK, "lora_down rank")
+    _need(out.dtype == torch.bfloat16 and out.is_contiguous() and out.dim() == 2 and out.shape[0] >= M and
+          out.shape[1] == r, "lora_down out bf16 [M, r]")
+    rec = _REC[0]
+    e0 = rec.begin() if rec is not None else None
+    _lib.call("vc_lora_down", _p(x), x.stride(0), M, K, _p(s), 1 if transposed else K, r if transposed else 1, r,
+              _p(out), _stream(x))
+    if rec is not None:
+        rec.end(e0, "lora::down_kernel", "lora_down", M * K * 2.0 + M * r * 2.0 + r * K * 4.0, "byte")
+    return out
+
+
+def lora_wgrad_work(N: int, r: int, device, splits: int = 32) -> torch.Tensor:
+    """Scratch for lora_wgrad's split partials (`splits` of them; the kernel takes what fits)."""
+    return torch.empty(splits * N * r, dtype=torch.float32, device=device)
+
+
+def lora_wgrad(g: torch.Tensor, u: torch.Tensor, out: torch.Tensor, work: torch.Tensor, c: float = 1.0,
+               m: int | None = None, transposed: bool | None = None) -> torch.Tensor:
+    """out = c * g[:m].T @ u[:m]: g bf16 [M, N] (unit column stride), u bf16 [M, r]; out f32 [N, r], or f32 [r, N]
+    (then the transpose is stored).  Split over M into `work`, partials summed in a fixed order."""
+    _dev(g, u, out, work)
+    M = g.shape[0] if m is None else m
+    N = g.shape[1]
+    _need(g.dtype == torch.bfloat16 and g.dim() == 2 and g.stride(1) == 1 and g.shape[0] >= M, "lora_wgrad g bf16 [M, N]")
+    _need(u.dtype == torch.bfloat16 and u.dim() == 2 and u.is_contiguous() and u.shape[0] >= M and
+          1 <= u.shape[1] <= LORA_MAX_RANK, "lora_wgrad u bf16 [M, r]")
+    r = u.shape[1]
+    _need(out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) in ((N, r), (r, N)),
+          "lora_wgrad out f32 [N, r] or [r, N]")
+    if transposed is None:
+        transposed = tuple(out.shape) != (N, r)
+    _need(tuple(out.shape) == ((r, N) if transposed else (N, r)), "lora_wgrad out shape against transposed")
+    _need(work.dtype == torch.float32 and work.is_contiguous() and work.numel() >= N * r, "lora_wgrad work")
+    rec = _REC[0]
+    e0 = rec.begin() if rec is not None else None
+    _lib.call("vc_lora_wgrad", _p(g), g.stride(0), _p(u), M, N, r, c, 1 if transposed else 0, _p(out), _p(work),
+              work.numel(), _stream(g))
+    if rec is not None:
+        rec.end(e0, "lora::wgrad_kernel (+ wgrad_reduce_kernel)", "lora_wgrad", M * N * 2.0 + M * r * 2.0 + N * r * 4.0,
+                "byte")
+    return out
+
+
+def lora_grads(x: torch.Tensor, dy: torch.Tensor, a: torch.Tensor, b: torch.Tensor, c: float, da: torch.Tensor,
+               db: torch.Tensor, uv: torch.Tensor, work: torch.Tensor, m: int | None = None):
+    """The gradients of one adapter (W_eff = W + s b a) from the saved input x bf16 [M, K] and the output
+    gradient dy bf16 [M, N]: db [N, r] = c dy^T (x a^T), da [r, K] = c (dy b)^T x, with c = s (times the q
+    scale for the q adapter).  uv: bf16 scratch of >= M * r elements for the r-wide intermediate (rounded to
+    bf16 once; the MFMAs also read a / b rounded to bf16); work: f32 split scratch.  No [N, K] gradient exists at
+    any point."""
+    N, K = dy.shape[1], x.shape[1]
+    r = _lora_ab("lora_grads", a, b, N, K)
+    M = x.shape[0] if m is None else m
+    _need(uv.dtype == torch.bfloat16 and uv.is_contiguous() and uv.numel() >= M * r, "lora_grads uv scratch")
+    _need(tuple(da.shape) == (r, K) and tuple(db.shape) == (N, r), "lora_grads da [r, K], db [N, r]")
+    u = uv.view(-1)[:M * r].view(M, r)
+    lora_down(x, a, u, m=M)
+    lora_wgrad(dy, u, db, work, c, m=M, transposed=False)
+    lora_down(dy, b, u, transposed=True, m=M)
+    lora_wgrad(x, u, da, work, c, m=M, transposed=True)
+
+
 # ---- ResNet50-LSTM (csrc/lstm.hip) ------------------------------------------------------------
 def lstm_group(hidden: int) -> int:
     """Sequences one workgroup of the recurrence kernels owns (csrc/lstm.hip group_of)."""

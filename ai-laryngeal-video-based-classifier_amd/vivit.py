@@ -138,6 +138,7 @@ class VivitForVideoClassification(torch.nn.Module):
         self._gflat = None     # gradients, same layout (p.grad are views)
         self._gscratch = None  # backward target when gradients accumulate across calls
         self._engine = None
+        self._lora = None      # vclip_amd.lora.LoraState while adapters are attached (lora.attach)
         self.grad_ready_hooks = []  # fn(stage, start, end, gflat): a slice of gflat is final (enqueued)
         self._packed = None
         self._ws = {}
@@ -216,6 +217,8 @@ class VivitForVideoClassification(torch.nn.Module):
     def _apply(self, fn, *args, **kwargs):  # .to() / .cuda(): parameters move one by one
         out = super()._apply(fn, *args, **kwargs)
         self._flat = self._gflat = self._gscratch = self._engine = None
+        if self._lora is not None:
+            self._lora.reset()
         self._packed = None
         self._ws = {}
         self._explain_ws = {}
@@ -240,19 +243,27 @@ class VivitForVideoClassification(torch.nn.Module):
                 # whole layout (its alignment gaps stay zero in both buffers: AdamW keeps them 0)
                 self.P(n)._vc_flat_layout = (self._layout.total, len(self._names))
         self._flat = flat
-        self._gflat = torch.zeros_like(flat)
+        # LoRA mode never writes a full-size gradient: the buffer is made by the first full backward
+        self._gflat = None if self._lora is not None else torch.zeros_like(flat)
         self._gscratch = None
         self._engine = None
 
     def _train_engine(self, B, device):
         self._ensure_flat(device)
+        if self._lora is not None:
+            self._lora.ensure_flat(self, device)
         if self._engine is None or self._engine.B != B or self._engine.device != device:
             self._engine = None
             self._engine = TrainEngine(self, B, device)
         return self._engine
 
     def _run_backward(self, eng, dlogits):
+        if self._lora is not None:
+            from . import lora
+            return lora.run_backward(self, eng, dlogits)
         params = self._param_list()
+        if self._gflat is None:  # flattened while adapters were attached (lora.merge since)
+            self._gflat = torch.zeros_like(self._flat)
         accumulate = any(p.grad is not None for p in params)
         if not accumulate:
             target = self._gflat
@@ -297,7 +308,10 @@ class VivitForVideoClassification(torch.nn.Module):
 
     def _weights_version(self):
         from . import vivit_train
-        return (vivit_train.MASTER_EPOCH[0], sum(p._version for p in self._param_list()))
+        ver = (vivit_train.MASTER_EPOCH[0], sum(p._version for p in self._param_list()))
+        if self._lora is not None:  # the adapters are part of the weights the packs are made from
+            ver += (id(self._lora), sum(p._version for p in self._lora.params(self)))
+        return ver
 
     # ---- device packing ----------------------------------------------------------
     def _pack(self, device):
@@ -315,6 +329,15 @@ class VivitForVideoClassification(torch.nn.Module):
         c = self.config
         f32 = torch.float32
         P = lambda n: self.P(n).detach().to(device)  # noqa: E731
+        if self._lora is not None:
+            # adapters attached: every adapted weight is vc_lora_merge's fp32 W + s B A, the tensor lora.merge
+            # writes into the masters, so the packs (and the logits) are those of the merged model
+            from . import lora
+            if npre > 0:
+                lora.refuse(self, "compute_dtype=float16 with precise_layers > 0")
+            adapted = self._lora.by_weight()
+            P = lambda n: (lora.merged_weight(self, n, device) if n in adapted  # noqa: E731
+                           else self.P(n).detach().to(device))
         D = c.hidden_size
         kt, kh, kw = c.tubelet_size
         pk = {"device": device, "version": ver, "dtype": bf, "precise": npre, "pops": pops}
@@ -429,6 +452,8 @@ class VivitForVideoClassification(torch.nn.Module):
                                "to cuda (the reference's `.to(device)`, trainer.py:92)")
         x = pixel_values.contiguous().float() if pixel_values.dtype != torch.float32 else pixel_values.contiguous()
         params = self._param_list()
+        if self._lora is not None:
+            params = params + self._lora.params(self)
         if self.training and torch.is_grad_enabled() and any(p.requires_grad for p in params):
             logits = VivitTrainFn.apply(self, x, *params)  # forward saving activations; HIP backward
         else:
@@ -787,6 +812,9 @@ class VivitForVideoClassification(torch.nn.Module):
             raise ValueError(f"pixel_values {tuple(pix.shape)} do not match config "
                              f"(T={c.num_frames}, C={c.num_channels}, {c.image_size}^2)")
         if method == "grad_rollout":
+            if self._lora is not None:
+                from . import lora
+                lora.refuse(self, "explain(method=\"grad_rollout\")")
             return self._explain_grad_rollout(pix, target, scalar_target)
         _, S, _, _ = self.geometry(B)
         Hn, nl = c.num_attention_heads, c.num_hidden_layers

@@ -109,13 +109,22 @@ class TrainEngine:
         # saved forward activations
         self.A_emb = z(Memb, self.Kemb)
         self.R = [z(Mpad, D, dt=f32) for _ in range(2 * L + 1)]  # residual stream before/after each block
-        self.Y1 = [z(Mpad, D) for _ in range(L)]
-        self.QKV = [z(Mpad, 3 * D) for _ in range(L)]
-        self.O = [z(Mpad, D) for _ in range(L)]
-        self.LSE = [z(B * H * S, dt=f32) for _ in range(L)]
-        self.Y2 = [z(Mpad, D) for _ in range(L)]
-        self.Hpre = [z(Mpad, I) for _ in range(L)]
-        self.Hd = [z(Mpad, I) for _ in range(L)]
+        # LoRA mode (vclip_amd.lora adapters attached): the backward stops at the lowest adapted layer l0, so the
+        # layers below it save nothing -- they all write one shared set of activation buffers
+        self.lora = getattr(model, "_lora", None)
+        l0 = self.lora.first_layer() if self.lora is not None else 0
+
+        def per_layer(*shape, dt=bf):
+            shared = z(*shape, dt=dt) if l0 > 0 else None
+            return [shared if i < l0 else z(*shape, dt=dt) for i in range(L)]
+
+        self.Y1 = per_layer(Mpad, D)
+        self.QKV = per_layer(Mpad, 3 * D)
+        self.O = per_layer(Mpad, D)
+        self.LSE = per_layer(B * H * S, dt=f32)
+        self.Y2 = per_layer(Mpad, D)
+        self.Hpre = per_layer(Mpad, I)
+        self.Hd = per_layer(Mpad, I)
         self.logits = z(B, c.num_labels, dt=f32)
         # backward scratch
         self.dX = z(Mpad, D, dt=f32)
@@ -151,10 +160,43 @@ class TrainEngine:
                        f2=z(D, I), f2T=z(I, D), bqkv=z(3 * D, dt=f32)) for _ in range(L)]
         self.W_emb = z(D, self.Kemb)
         self.kernel_events = None
+        if self.lora is not None:
+            st = self.lora
+            # the adapters' fp32 masters (views of the small flat buffer), the r-wide bf16 intermediate of their
+            # gradients, and where the frozen parameters' LayerNorm / head gradients go (computed by kernels that
+            # have no switch for them, never read)
+            self.lora_ab = {k: (st.view(st.flat, v[0]), st.view(st.flat, v[1])) for k, v in st.adapters.items()}
+            self.lora_uv = z(Mpad * st.rank)
+            self.lora_scratch = z(4, D, dt=f32)
+            self.lora_head_scratch = z(c.num_labels * D + c.num_labels, dt=f32)
+            self._frozen_packed = None  # version of the base weights the bf16 packs were made from
 
     # ---- weights ------------------------------------------------------------------------------
     def pack(self):
-        """fp32 masters -> bf16 operands (every step: the optimizer moved the masters)."""
+        """fp32 masters -> bf16 operands (every step: the optimizer moved the masters).  LoRA mode: the frozen
+        base weights are packed once (again when their version counters move: load_state_dict, an in-place edit)
+        and every step only the adapted weights are rebuilt, as W + s B A, by vc_lora_merge."""
+        if self.lora is None:
+            return self._pack_base()
+        m, st = self.model, self.lora
+        lay, flat = m._layout, m._flat
+        D = self.D
+        ver = (flat.data_ptr(), sum(q._version for q in m._param_list()))
+        if self._frozen_packed != ver:
+            self._pack_base()
+            self._frozen_packed = ver
+        qs = (D // self.H) ** -0.5 * ops.LOG2E
+        for (i, t), (a, b) in self.lora_ab.items():
+            p = f"vivit.layers.{i}."
+            W = self.W[i]
+            if t in ("q", "k", "v"):
+                wqkv = lay.span(flat, p + "attention.q_proj.weight", 3 * D * D, (3 * D, D))
+                ops.lora_merge(wqkv, a, b, st.s, W["qkv"], W["qkvT"], row0=D * "qkv".index(t), nscaled=D, scale=qs)
+            else:
+                name, key = {"o": ("attention.o_proj", "o"), "fc1": ("mlp.fc1", "f1"), "fc2": ("mlp.fc2", "f2")}[t]
+                ops.lora_merge(lay.view(flat, p + name + ".weight"), a, b, st.s, W[key], W[key + "T"])
+
+    def _pack_base(self):
         lay, flat = self.model._layout, self.model._flat
         D = self.D
         qs = (D // self.H) ** -0.5 * ops.LOG2E
@@ -321,6 +363,99 @@ class TrainEngine:
         ready(*stages["embeddings"])
 
 
+    def backward_lora(self, dlogits: torch.Tensor, gflat: torch.Tensor, ghead: torch.Tensor):
+        """LoRA mode's backward: the data-gradient chain of `backward` without any weight, bias or LayerNorm
+        parameter gradient; each adapter's dA / dB (ops.lora_grads, on the side stream where the weight gradients
+        run otherwise) into gflat (the adapters' flat layout), the classifier's into ghead when it trains.  The
+        chain ends as soon as the lowest adapted layer's last adapter gradient is enqueued."""
+        m, st, lay, flat = self.model, self.lora, self.model._layout, self.model._flat
+        c = m.config
+        D, I, S, B, H = self.D, self.I, self.S, self.B, self.H
+        eps = c.layer_norm_eps
+        qs = (D // H) ** -0.5 * ops.LOG2E
+        P = lambda n: lay.view(flat, n)  # noqa: E731
+        dX, dXa, dXb, dY, dH, dO, dQKV = self.dX, self.dXb, self.dXb2, self.dY, self.dH, self.dO, self.dQKV
+        main = torch.cuda.current_stream(self.device)
+        side_on = self.side_wgrad
+        if side_on and self.side is None:
+            self.side = streams.pick_streams(self.device, 3, against=(main,))[0]
+        work = self.work_side if side_on else self.work
+        scr = self.lora_scratch
+
+        def on_side(fn):
+            if not side_on:
+                fn()
+                return None
+            self.side.wait_stream(main)
+            with torch.cuda.stream(self.side):
+                fn()
+            e = torch.cuda.Event()
+            e.record(self.side)
+            return e
+
+        def wait(e):
+            if e is not None:
+                main.wait_event(e)
+
+        def adapter(i, t, x, dy, cc):
+            a, b = self.lora_ab[(i, t)]
+            na, nb = st.adapters[(i, t)][:2]
+            ops.lora_grads(x, dy, a, b, cc, st.view(gflat, na), st.view(gflat, nb), self.lora_uv, work)
+
+        gc = lambda name: self.gemm_cfg.get(name, -1)  # noqa: E731
+        if st.train_head:
+            gw, gb = st.head_views(m, ghead)
+        else:
+            gw, gb = st.head_views(m, self.lora_head_scratch)
+        dX.zero_()
+        dXa.zero_()
+        ops.cls_head_bwd(self.R[2 * self.L], B, S, P("vivit.layernorm.weight"), P("vivit.layernorm.bias"), eps,
+                         P("classifier.weight"), dlogits, dX, dXa, gw, gb, scr[0], scr[1])
+        l0 = st.first_layer()
+        ev_fc1 = ev_o = ev_qkv = None
+        for i in reversed(range(l0, self.L)):
+            p = f"vivit.layers.{i}."
+            W = self.W[i]
+            ad = [t for t in st.targets if (i, t) in st.adapters]
+            qkv = [t for t in ("q", "k", "v") if t in ad]
+            stages = [g for g in ("fc2", "fc1", "o") if g in ad] + (["qkv"] if qkv else [])
+            stop = stages[-1] if i == l0 else None  # the lowest adapted layer: nothing below its last adapter
+            ev_fc2 = on_side(lambda: adapter(i, "fc2", self.Hd[i], dXa, st.s)) if "fc2" in ad else None
+            if stop == "fc2":
+                break
+            wait(ev_fc1)  # dH was read by the layer above's fc1 adapter gradients
+            ops.gemm(dXa, W["f2T"], self.zeros[:I], "dgelu_tanh", dH, aux=self.Hpre[i], cfg=gc("dgelu"),
+                     op=f"dgrad.l{i}.fc2")
+            ev_fc1 = on_side(lambda: adapter(i, "fc1", self.Y2[i], dH, st.s)) if "fc1" in ad else None
+            if stop == "fc1":
+                break
+            ops.gemm(dH, W["f1T"], self.zeros[:D], "bias_f32", dY, cfg=gc("dfc1"), op=f"dgrad.l{i}.fc1")
+            wait(ev_o)  # dXb was read by the layer above's o_proj adapter gradients
+            ops.layernorm_bwd(dY, self.R[2 * i + 1], P(p + "layernorm_after.weight"), eps, dX, dXb, scr[2], scr[3],
+                              self.work, m=B * S)
+            ev_o = on_side(lambda: adapter(i, "o", self.O[i], dXb, st.s)) if "o" in ad else None
+            if stop == "o":
+                break
+            ops.gemm(dXb, W["oT"], self.zeros[:D], "bias", dO, cfg=gc("do"), op=f"dgrad.l{i}.o")
+            wait(ev_qkv)  # dQKV was read by the layer above's q / k / v adapter gradients
+            if self.attn_bwd_2s and self.side_dq is None:
+                self.side_dq = streams.pick_streams(self.device, 3, against=(main,))[1]
+            ops.attention_bwd(self.QKV[i], self.O[i], dO, self.LSE[i], self.delta, B, S, H, dQKV,
+                              stream2=self.side_dq if self.attn_bwd_2s else None)
+            # dQKV's q columns are the gradient of the scaled q the attention kernel reads: its adapter takes the
+            # q scale as the weight gradient's q rows do (nscaled / scale of ops.wgrad)
+            ev_qkv = on_side(lambda: [adapter(i, t, self.Y1[i], dQKV[:, D * "qkv".index(t):D * ("qkv".index(t) + 1)],
+                                              st.s * (qs if t == "q" else 1.0)) for t in qkv]) if qkv else None
+            if stop == "qkv":
+                break
+            ops.gemm(dQKV, W["qkvT"], self.zeros[:D], "bias_f32", dY, cfg=gc("dqkv"), op=f"dgrad.l{i}.qkv")
+            wait(ev_fc2)  # dXa was read by this layer's fc2 adapter gradients
+            ops.layernorm_bwd(dY, self.R[2 * i], P(p + "layernorm_before.weight"), eps, dX, dXa, scr[2], scr[3],
+                              self.work, m=B * S)
+        if side_on:
+            main.wait_stream(self.side)
+
+
 class VivitTrainFn(torch.autograd.Function):
     """logits = ViViT(pixel_values) with the HIP forward; backward = the HIP backward, which
     writes the parameter gradients into the model's flat gradient buffer itself (p.grad are
@@ -330,14 +465,14 @@ class VivitTrainFn(torch.autograd.Function):
     def forward(ctx, model, pix, *params):
         eng = model._train_engine(pix.shape[0], pix.device)
         logits = eng.forward(pix)
-        ctx.model, ctx.engine = model, eng
+        ctx.model, ctx.engine, ctx.nparams = model, eng, len(params)
         return logits.clone()
 
     @staticmethod
     def backward(ctx, dlogits):
         model, eng = ctx.model, ctx.engine
         model._run_backward(eng, dlogits.float().contiguous())
-        return (None, None) + (None,) * len(model._param_list())
+        return (None, None) + (None,) * ctx.nparams
 
 
 class GraphedTrainStep:
@@ -365,6 +500,9 @@ class GraphedTrainStep:
         from .optim import AdamW
         if not isinstance(optimizer, AdamW):
             raise TypeError("GraphedTrainStep needs vclip_amd.optim.AdamW")
+        if getattr(model, "_lora", None) is not None:
+            raise NotImplementedError("GraphedTrainStep is not supported with LoRA adapters attached; "
+                                      "lora.merge(model) first")
         if model.grad_ready_hooks:
             raise RuntimeError("GraphedTrainStep: grad_ready_hooks (data-parallel all-reduce) run eagerly")
         if len(optimizer.param_groups) != 1:

@@ -782,6 +782,37 @@ int vc_adamw_multi(const int64_t* table, int64_t ntab, int64_t nchunks, float lr
 int vc_pack_weight(const float* src, int64_t N, int64_t K, int64_t nscaled, float scale, uint16_t* dst, uint16_t* dstT,
                    hipStream_t stream);
 
+/* ---- LoRA fine-tuning of the ViViT train step (csrc/lora.hip): W_eff = W + s B A, 1 <= r <= 64 ---- */
+
+/*
+ * Rows n in [row0, row0 + rows) of v[n][k] = W[n][k] + s * sum_j B[n - row0][j] A[j][k], fp32, j ascending.
+ * W f32 [.., ldw], A f32 [r][K], B f32 [rows][r] (contiguous).  Any of three outputs (null: not written), all
+ * addressed by the absolute row n: dst bf16 [.., ldd], dstT bf16 [K][ldt] (column n), out f32 [.., ldo].  Rows
+ * n < nscaled are multiplied by scale in the bf16 outputs only (vc_pack_weight's rule; with B = 0 the bf16
+ * outputs are vc_pack_weight's bits).  row0, rows, K and the leading dimensions % 4 == 0; W / out 16-byte,
+ * dst / dstT 8-byte aligned.  out may not alias W.
+ */
+int vc_lora_merge(const float* W, int64_t ldw, int64_t row0, int64_t rows, int64_t K, const float* A, const float* B,
+                  int64_t r, float s, int64_t nscaled, float scale, uint16_t* dst, int64_t ldd, uint16_t* dstT,
+                  int64_t ldt, float* out, int64_t ldo, hipStream_t stream);
+
+/*
+ * U[m][j] = bf16(sum_k X[m][k] bf16(S[j][k])), fp32 accumulation on the 16x16x32 bf16 MFMA in a fixed order.  X bf16
+ * [M][ldx] (K columns), U bf16 [M][r] contiguous, S f32 with element (j, k) at S[j sj + k sk]: A [r][K] (sj = K,
+ * sk = 1) or B [K][r] read transposed (sj = 1, sk = r); S is rounded to bf16 (the MFMA's operand type) as it is read.  K % 32 == 0,
+ * ldx % 8 == 0; X and an [r][K] S 16-byte aligned.
+ */
+int vc_lora_down(const uint16_t* X, int64_t ldx, int64_t M, int64_t K, const float* S, int64_t sj, int64_t sk,
+                 int64_t r, uint16_t* U, hipStream_t stream);
+
+/*
+ * out[n][j] (transposed != 0: out[j][n]) = c * sum_m G[m][n] U[m][j].  G bf16 [M][ldg] (N columns), U bf16 [M][r],
+ * out f32 contiguous.  M is split over workgroups into `work` (f32, >= N r elements; more allows more splits) and
+ * the partials are summed in split order by a second kernel: no atomics, bit-reproducible.  N, ldg % 2 == 0.
+ */
+int vc_lora_wgrad(const uint16_t* G, int64_t ldg, const uint16_t* U, int64_t M, int64_t N, int64_t r, float c,
+                  int transposed, float* out, float* work, int64_t work_elems, hipStream_t stream);
+
 /* ---- ResNet50-LSTM (resnet50-2d-lstm/src/models/model.py:5-60, trainer.py:156-170), csrc/lstm.hip ---- */
 
 /*
