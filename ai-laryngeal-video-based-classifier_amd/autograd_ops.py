@@ -39,11 +39,8 @@ import ctypes
 import torch
 
 from . import _lib, ops
+from .hosting import round_up as _round_up
 from .ops import _p, _stream
-
-
-def _round_up(x: int, m: int) -> int:
-    return (x + m - 1) // m * m
 
 
 def _padded(x: torch.Tensor, rows: int, dtype=None) -> torch.Tensor:

@@ -16,12 +16,10 @@ oracle/resnet3d_ref.py, the restatement of pytorchvideo's create_resnet (SURVEY.
 """
 from __future__ import annotations
 
-from collections import OrderedDict
-
-import numpy as np
 import torch
 
-from . import ops, streams
+from . import ops
+from .hosting import FusedVideoModel, round_up as _ru
 from .weights import resnet3d_param_shapes
 
 RESNET3D_50 = dict(depths=(3, 4, 6, 3), stem_dim=64, conv_a_kernels=((1, 1, 1), (1, 1, 1), (3, 1, 1), (3, 1, 1)),
@@ -29,34 +27,14 @@ RESNET3D_50 = dict(depths=(3, 4, 6, 3), stem_dim=64, conv_a_kernels=((1, 1, 1), 
                    stem_kernel=(3, 7, 7), stem_pad=(1, 3, 3))
 
 
-def _ru(x, m):
-    return (x + m - 1) // m * m
-
-
-class ResNet3d(torch.nn.Module):
+class ResNet3d(FusedVideoModel):
     """fp32 master parameters + BatchNorm running statistics in pytorchvideo naming."""
 
     def __init__(self, cfg: dict = RESNET3D_50):
-        super().__init__()
+        # BatchNorm running statistics are buffers in pytorchvideo: no gradient, updated by the train step
+        super().__init__(resnet3d_param_shapes(dict(cfg)), cfg.get("num_classes", 2),
+                         frozen=lambda n: n.endswith("running_mean") or n.endswith("running_var"))
         self.cfg = dict(cfg)
-        shapes = resnet3d_param_shapes(self.cfg)
-        self._names = list(shapes.keys())
-        self.params = torch.nn.ParameterDict()
-        for n, s in shapes.items():
-            # BatchNorm running statistics are buffers in pytorchvideo: no gradient, updated by the train step
-            stat = n.endswith("running_mean") or n.endswith("running_var")
-            self.params[n.replace(".", "__")] = torch.nn.Parameter(torch.zeros(s), requires_grad=not stat)
-        self._packed = None
-        self._ws = {}
-        self._ws_used = []
-        self.concurrent_streams = None  # n > 1: the inference batch split over n HIP streams (vclip_amd.streams)
-        self.split_sizes = None  # clips per stream part (streams.run_split); None = as even as possible
-        self._streams = None
-        self._split_out = {}
-        # True: the inference forward is captured once per input / configuration into a hipGraph and
-        # replayed (streams.GraphReplay); bit-identical logits
-        self.graph_replay = False
-        self._graphs = None
         self.head_dropout = True  # train step: the head's Dropout(0.5) (pytorchvideo create_resnet dropout_rate)
         # inference convolutions other than 1x1x1 stride 1 as implicit GEMMs (vc_conv3d_gemm_bf16: the
         # A rows gathered from the activations per kernel tap, no im2col buffer); False: im2col + GEMM.
@@ -70,44 +48,19 @@ class ResNet3d(torch.nn.Module):
         # per-convolution overrides {"conv_a.s4": (ring, tile), ...} of vc_conv3d_gemm_bf16_cfg (tile 0 auto,
         # 1 = 64 x 128, 2 = 128 x 128; ring 0 auto, 2, 3, 4); bit-identical for any setting
         self.conv_cfg = {}
-        self._explain_ws = {}  # explain's kept activations and gradient buffers per (B, geometry, layer, device)
 
     def _conv_kw(self, op: str, s: int) -> dict:
         ring, tile = self.conv_cfg.get(op, (self.conv_ring.get(f"s{s + 2}", 0), 0))
         return dict(ring=ring, tile=tile)
 
-    def state_dict(self, *a, **k):
-        return OrderedDict((n, self.params[n.replace(".", "__")].detach()) for n in self._names)
-
-    def load_state_dict(self, sd, strict: bool = True):
-        sd = {k[len("module."):] if k.startswith("module.") else k: v for k, v in sd.items()}
-        sd = {k: v for k, v in sd.items() if not k.endswith("num_batches_tracked")}
-        missing = [n for n in self._names if n not in sd]
-        unexpected = [k for k in sd if k not in self._names]
-        if strict and (missing or unexpected):
-            raise KeyError(f"load_state_dict: missing={missing[:5]} unexpected={unexpected[:5]}")
-        with torch.no_grad():
-            for n in self._names:
-                if n in sd:
-                    v = sd[n]
-                    v = torch.as_tensor(np.asarray(v)) if not isinstance(v, torch.Tensor) else v
-                    dst = self.params[n.replace(".", "__")]
-                    dst.copy_(v.reshape(dst.shape))
-        self._packed = None
-        return missing, unexpected
+    def _clean_state_dict(self, sd):
+        return {k: v for k, v in super()._clean_state_dict(sd).items() if not k.endswith("num_batches_tracked")}
 
     # ---- packing: BN folded, weights [N_pad, K] bf16 in the im2col column order --------
-    def P(self, name):
-        return self.params[name.replace(".", "__")]
-
-    def _weights_version(self):
-        from . import vivit_train
-        return (vivit_train.MASTER_EPOCH[0], sum(p._version for p in self.params.values()))
-
     def _pack(self, device):
-        ver = self._weights_version()  # the fused AdamW updates in place without bumping _version
-        if self._packed is not None and self._packed["device"] == device and self._packed["version"] == ver:
-            return self._packed
+        pk = self._cached_pack(device)
+        if pk is not None:
+            return pk
         ops.zero_row(device)  # the implicit convs' padding row, zeroed on the caller's stream before any fork
         c = self.cfg
         eps = c["bn_eps"]
@@ -127,7 +80,7 @@ class ResNet3d(torch.nn.Module):
             B[:b.numel()] = b
             return W.to(torch.bfloat16).contiguous(), B.float().contiguous()
 
-        pk = {"device": device, "version": ver}
+        pk = {"device": device, "version": self._weights_version()}
         sk = c.get("stem_kernel", (3, 7, 7))
         pk["stem"] = fold("blocks.0.conv", "blocks.0.norm", channels_last=False, k_pad=_ru(3 * sk[0] * sk[1] * sk[2], 64))
         if sk[2] <= 8:
@@ -175,14 +128,10 @@ class ResNet3d(torch.nn.Module):
         return stem, g
 
     def _workspace(self, B, T, H, W, device, part: int = 0):
-        key = (B, T, H, W, str(device), part)
-        if key in self._ws:
-            ws = self._ws[key]
-            if not any(w is ws for w in self._ws_used):
-                self._ws_used.append(ws)
-            return ws
-        if len(self._ws) >= 4:
-            self._ws = {}
+        return self._cached_workspace((B, T, H, W, str(device), part),
+                                      lambda: self._make_workspace(B, T, H, W, device), 4)
+
+    def _make_workspace(self, B, T, H, W, device):
         c = self.cfg
         stem, grids = self.geometry(T, H, W)
         bf = torch.bfloat16
@@ -218,8 +167,6 @@ class ResNet3d(torch.nn.Module):
         ws["col_elems"] = big
         ws["head_work"] = torch.zeros(B * T * 2048 * 33, dtype=torch.float32, device=device)
         ws["logits"] = torch.zeros((B, c["num_classes"]), dtype=torch.float32, device=device)
-        self._ws[key] = ws
-        self._ws_used.append(ws)
         return ws
 
     # ---- forward -----------------------------------------------------------------------
@@ -318,31 +265,12 @@ class ResNet3d(torch.nn.Module):
             g_in = g
         return x, B, grids[-1], cin
 
-    def forward_logits(self, video: torch.Tensor) -> torch.Tensor:
-        """logits f32 [B, classes] (a workspace buffer, overwritten by the next call); with
-        `concurrent_streams = n > 1` the batch is split over n HIP streams (vclip_amd.streams) and with
-        `graph_replay` the forward is replayed from a captured hipGraph (bit-identical either way)."""
+    def _check_input(self, video):
         if video.shape[1] != 3:
             raise ValueError("video must be [B, 3, T, H, W]")
-        if self.graph_replay and not streams.serial() and not torch.cuda.is_current_stream_capturing():
-            from .streams import GraphReplay
-            if self._graphs is None:
-                self._graphs = GraphReplay()
-            key = (video.data_ptr(), tuple(video.shape), tuple(video.stride()), video.dtype, self.concurrent_streams, None if self.split_sizes is None else tuple(self.split_sizes),
-                   self.implicit_conv, tuple(sorted(self.conv_ring.items())), tuple(sorted(self.conv_cfg.items())),
-                   str(video.device), self._weights_version())
-            return self._graphs.run(key, video, self._forward_eager, keep=lambda: (self._packed, tuple(self._ws_used)))
-        return self._forward_eager(video)
 
-    def _forward_eager(self, video: torch.Tensor) -> torch.Tensor:
-        self._ws_used = []  # the workspaces this forward addresses (a captured graph keeps exactly these)
-        B = video.shape[0]
-        ns = max(1, min(int(self.concurrent_streams or 1), B))
-        if ns == 1:
-            return self._forward_part(video, 0)
-        from .streams import run_split
-        return run_split(self, video, ns, self._forward_part, self.cfg["num_classes"],
-                         prepare=lambda: self._pack(video.device))
+    def _graph_knobs(self):
+        return (self.implicit_conv, tuple(sorted(self.conv_ring.items())), tuple(sorted(self.conv_cfg.items())))
 
     def _forward_part(self, video: torch.Tensor, part: int, out=None, keep=None) -> torch.Tensor:
         """keep (explain only): forward_features' keep buffers; the head then pools in keep["head_work"]"""

@@ -44,7 +44,8 @@ import torch
 
 from . import autograd_ops as A
 from . import ops
-from .resnet3d import ResNet3d, _ru
+from .hosting import ParamStore, round_up as _ru
+from .resnet3d import ResNet3d
 from .weights import RESNET50_2D, blocks_to_torchvision_resnet50, resnet50_lstm_param_shapes, \
     torchvision_resnet50_to_blocks
 
@@ -61,7 +62,7 @@ class LstmState(NamedTuple):
         return LstmState(self.h.detach().clone(), self.c.detach().clone())
 
 
-class VideoResNet50LSTM(torch.nn.Module):
+class VideoResNet50LSTM(ParamStore):
     def __init__(self, hidden_size: int = 256, num_layers: int = 2, dropout: float = 0.5,
                  freeze_backbone_bn: bool = False):
         super().__init__()
@@ -80,19 +81,12 @@ class VideoResNet50LSTM(torch.nn.Module):
             p.requires_grad_(False)  # model.py:15-16
         shapes = resnet50_lstm_param_shapes(hidden_size, num_layers)
         self._all_names = list(shapes.keys())
-        self._names = [n for n in shapes if not n.startswith("resnet50.")]
-        self.params = torch.nn.ParameterDict()
-        for n in self._names:
-            self.params[n.replace(".", "__")] = torch.nn.Parameter(torch.zeros(shapes[n]), requires_grad=True)
-        self._packed = None
+        self._init_params({n: s for n, s in shapes.items() if not n.startswith("resnet50.")})
         self._ws = {}
         # the last forward's bf16 feature matrix [B*T, 2048] and dropout masks ({"lstm": [per layer or None],
         # "head": mask or None}), for tests that replay them through an oracle
         self.last_features = None
         self.last_keep = None
-
-    def P(self, name):
-        return self.params[name.replace(".", "__")]
 
     # ---- state dict in the reference's naming -----------------------------------------
     def state_dict(self, *a, **k):
@@ -134,15 +128,11 @@ class VideoResNet50LSTM(torch.nn.Module):
         return m1 + missing, u1 + unexpected
 
     # ---- operand images of the LSTM / head weights, once per weights version -----------
-    def _weights_version(self):
-        from . import vivit_train
-        return (vivit_train.MASTER_EPOCH[0], sum(p._version for p in self.params.values()))
-
     def _pack(self, device):
-        ver = self._weights_version()  # the fused AdamW updates in place without bumping _version
-        if self._packed is not None and self._packed["device"] == device and self._packed["version"] == ver:
-            return self._packed
-        pk = {"device": device, "version": ver, "layers": []}
+        pk = self._cached_pack(device)
+        if pk is not None:
+            return pk
+        pk = {"device": device, "version": self._weights_version(), "layers": []}
         for l in range(self.layers):
             L = A.pack_lstm_weights(self.P(f"lstm.weight_ih_l{l}"), self.P(f"lstm.weight_hh_l{l}"))
             b = torch.zeros(L["wb"].shape[0], dtype=torch.float32, device=device)

@@ -8,6 +8,7 @@ kernels (ViViT-B B = 8: 840 -> 916 clips/s with 2 streams, tools/exp_streams.py,
 from __future__ import annotations
 
 import contextlib
+import threading
 import time
 
 import torch
@@ -161,9 +162,27 @@ TUNE_CANDIDATES = [6]
 # priority patterns of the fresh candidate sets, in rotation: (part index, part count) -> priority
 TUNE_PRIORITIES = [lambda i, n: 0, lambda i, n: -1 if i == 0 else 0]
 
-# set by GraphReplay while it captures a split forward: fork_parts then captures each part into a graph of
-# its own (stream, graph) instead of running it
-_PART_CAPTURE = [None]
+
+class _CaptureState(threading.local):
+    """What GraphReplay._capture sets around the forwards it runs for its own purposes, per thread: a split
+    forward another thread runs meanwhile sees the defaults (no capture, tuning allowed).
+    parts: the list fork_parts appends each part's (stream, graph) to instead of running the part;
+    no_tune: part_streams returns the cached pick without timing stream sets."""
+    parts = None
+    no_tune = False
+
+
+_CAPTURE = _CaptureState()
+
+
+@contextlib.contextmanager
+def _capturing(parts=None):
+    prev = _CAPTURE.parts, _CAPTURE.no_tune
+    _CAPTURE.parts, _CAPTURE.no_tune = parts, True
+    try:
+        yield
+    finally:
+        _CAPTURE.parts, _CAPTURE.no_tune = prev
 
 
 def fork_parts(sts, cur, fns) -> None:
@@ -171,7 +190,7 @@ def fork_parts(sts, cur, fns) -> None:
     Under GraphReplay's capture each part becomes a graph of its own, replayed on its own stream: one
     graph holding both branches runs them on queues HIP picks at instantiation, which serialized the
     parts in about half the processes (tools/exp_vivit_hwq.py)."""
-    cap = _PART_CAPTURE[0]
+    cap = _CAPTURE.parts
     for st, fn in zip(sts, fns):
         st.wait_stream(cur)
         with torch.cuda.stream(st):
@@ -214,10 +233,9 @@ def _candidate_sets(device, n, first):
                             for t in range(TUNE_CANDIDATES[0] - 1)]
 
 
-# eager split forwards tune their part streams on the first call per configuration (EAGER_TUNE); _NO_TUNE > 0
-# while GraphReplay runs a forward for its own purposes (its warm-up and part-capture passes)
+# eager split forwards tune their part streams on the first call per configuration (EAGER_TUNE), except
+# while GraphReplay runs a forward for its own purposes (_capturing: its warm-up and part-capture passes)
 EAGER_TUNE = [True]
-_NO_TUNE = [0]
 
 
 def part_streams(owner, key, n: int, run, device, priorities=None) -> list:
@@ -226,7 +244,7 @@ def part_streams(owner, key, n: int, run, device, priorities=None) -> list:
     stream set) is timed on the sets _candidate_sets gives and the fastest is kept for this owner and key
     (`owner.eager_tune_log`: (priorities, ms) per set); later calls reuse it.  Untuned (the cached
     pick_streams set) while instrumented (serial parts, an op recorder, kernel events), inside a capture,
-    or under _NO_TUNE.  The eager ViViT-B B = 8 two-stream forward ran 850-885 clips/s instead of
+    or under _capturing.  The eager ViViT-B B = 8 two-stream forward ran 850-885 clips/s instead of
     930-970 in about one process in five on the cached pick alone (tools/exp_vivit_hwq.py)."""
     if priorities is not None:
         return pick_streams(device, n, tuple(priorities)[:n])
@@ -235,7 +253,7 @@ def part_streams(owner, key, n: int, run, device, priorities=None) -> list:
     if got is not None:
         return got
     base = pick_streams(device, n)
-    if (n <= 1 or not EAGER_TUNE[0] or _NO_TUNE[0] or _SERIAL[0] or ops._REC[0] is not None
+    if (n <= 1 or not EAGER_TUNE[0] or _CAPTURE.no_tune or _SERIAL[0] or ops._REC[0] is not None
             or getattr(owner, "kernel_events", None) is not None or torch.cuda.is_current_stream_capturing()):
         return base
     cands = _candidate_sets(device, n, base)
@@ -245,9 +263,12 @@ def part_streams(owner, key, n: int, run, device, priorities=None) -> list:
     return cands[k]
 
 
-def run_split(owner, x: torch.Tensor, ns: int, part_fn, num_labels: int, prepare=None) -> torch.Tensor:
-    """part_fn(x_part, part_index, out=logits_rows) for each of `ns` contiguous batch parts, part i on
-    owner._streams[i]; returns the [B, num_labels] logits (a buffer of `owner`, reused per call).
+def run_split(owner, x: torch.Tensor, ns: int, part_fn, num_labels: int, prepare=None, sizes=None, key_extra=(),
+              **part_kw) -> torch.Tensor:
+    """part_fn(x_part, part_index, out=logits_rows, **part_kw) for each of `ns` contiguous batch parts, part i
+    on owner._streams[i]; returns the [B, num_labels] logits (a buffer of `owner`, reused per call).
+    `sizes`: clips per part (None = as even as possible; owner.last_split records them); `key_extra`: what
+    else part_streams' tuning is keyed by (whatever changes the parts' kernels at one batch split).
 
     `prepare()` builds the state every part reads (packed weights, bias caches) on the CALLER's
     stream before the fork: built inside part 0 on stream 0, it would be read by parts 1..n-1 on
@@ -263,20 +284,27 @@ def run_split(owner, x: torch.Tensor, ns: int, part_fn, num_labels: int, prepare
         owner._split_out[key] = torch.zeros(B, num_labels, dtype=torch.float32, device=dev)
     logits = owner._split_out[key]
     cur = torch.cuda.current_stream(dev)
-    bounds = split_bounds(B, ns, getattr(owner, "split_sizes", None))  # clips per part; None = as even as possible
-    if _SERIAL[0]:
+    bounds = split_bounds(B, ns, sizes)
+    owner.last_split = [bounds[i + 1] - bounds[i] for i in range(ns)]
+
+    def part(i):
+        return part_fn(x[bounds[i]:bounds[i + 1]], i, out=logits[bounds[i]:bounds[i + 1]], **part_kw)
+
+    if _SERIAL[0]:  # instrumentation: the parts one after the other on the caller's stream
         for i in range(ns):
-            part_fn(x[bounds[i]:bounds[i + 1]], i, out=logits[bounds[i]:bounds[i + 1]])
+            part(i)
         return logits
 
+    # whole parts enqueued one after the other (measured on ViViT-B, tools/exp_streams.py: enqueueing the
+    # parts layer by layer round robin ran 725 vs 911 clips/s, chaining their attention launches across
+    # the streams 721, and starting part i+1 at a fixed op of part i's first layer 887-906)
     def go(sts):
         for st in sts:
             x.record_stream(st)  # x may be freed by the caller while the side streams still read it
-        fork_parts(sts, cur, [lambda i=i: part_fn(x[bounds[i]:bounds[i + 1]], i, out=logits[bounds[i]:bounds[i + 1]])
-                              for i in range(ns)])
+        fork_parts(sts, cur, [lambda i=i: part(i) for i in range(ns)])
 
-    owner._streams = part_streams(owner, (B, ns, str(dev), tuple(bounds)), ns, go, dev,
-                                  getattr(owner, "stream_priorities", None))
+    owner._streams = part_streams(owner, (B, ns, str(dev), tuple(bounds)) + tuple(key_extra), ns, go, dev,
+                                  owner.stream_priorities)
     go(owner._streams)
     return logits
 
@@ -317,25 +345,16 @@ class GraphReplay:
         cur = torch.cuda.current_stream(dev)
         side = torch.cuda.Stream(device=dev)
         side.wait_stream(cur)
-        _NO_TUNE[0] += 1
-        try:
-            with torch.cuda.stream(side):
-                forward(x)  # first launches (kernel attributes), packing and workspaces outside the capture
-        finally:
-            _NO_TUNE[0] -= 1
+        with _capturing(), torch.cuda.stream(side):
+            forward(x)  # first launches (kernel attributes), packing and workspaces outside the capture
         cur.wait_stream(side)
         torch.cuda.synchronize(dev)
         # a split forward (fork_parts) first: each part captured into a graph of its own on its own
         # stream, everything outside the parts (cached packing) run eagerly -- it queues no kernel on a
         # repeat call, so the part graphs are the whole forward
         parts = []
-        _PART_CAPTURE[0] = parts if PART_GRAPHS[0] else None
-        _NO_TUNE[0] += 1
-        try:
+        with _capturing(parts if PART_GRAPHS[0] else None):
             out = forward(x)
-        finally:
-            _PART_CAPTURE[0] = None
-            _NO_TUNE[0] -= 1
         torch.cuda.synchronize(dev)
         if parts:
             g = self._tune(parts, dev)

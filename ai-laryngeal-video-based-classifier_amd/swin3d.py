@@ -23,12 +23,11 @@ oracle/swin3d_ref.py, the restatement of torchvision's algorithm (SURVEY.md §8c
 from __future__ import annotations
 
 import math
-from collections import OrderedDict
 
-import numpy as np
 import torch
 
-from . import ops, streams
+from . import ops
+from .hosting import FusedVideoModel, round_up as _ru
 from .weights import swin3d_param_shapes
 
 LOG2E = ops.LOG2E
@@ -45,10 +44,6 @@ SWIN3D_CONFIGS = {
                  window_size=(8, 7, 7), mlp_ratio=4.0, layer_norm_eps=1e-5, stochastic_depth_prob=0.1),
 }
 SWIN3D_CONFIGS["base_in22k"] = SWIN3D_CONFIGS["base"]
-
-
-def _ru(x, m):
-    return (x + m - 1) // m * m
 
 
 def relative_position_index(window_size):
@@ -161,70 +156,32 @@ def expand_bias_mb(table, full_window, window, device):
     return g.t().to(torch.float16).contiguous().view(heads, npad // 32, npad // 64, 2, 2, 64, 8)
 
 
-class Swin3d(torch.nn.Module):
+class Swin3d(FusedVideoModel):
     """fp32 master parameters in torchvision naming; bf16 / fp32 packed device copies."""
 
     def __init__(self, cfg: dict, num_classes: int = 2):
-        super().__init__()
-        self.cfg = dict(cfg, num_classes=num_classes)
-        self.num_classes = num_classes
         for h, C in zip(cfg["num_heads"], (cfg["embed_dim"] * 2 ** s for s in range(len(cfg["depths"])))):
             if C // h != 32:
                 raise ValueError("libvclip window attention supports head_dim 32 only")
-        shapes = swin3d_param_shapes(self.cfg)
-        self._names = list(shapes.keys())
-        self.params = torch.nn.ParameterDict()
-        for n, s in shapes.items():
-            self.params[n.replace(".", "__")] = torch.nn.Parameter(torch.zeros(s))
-        self._packed = None
+        super().__init__(swin3d_param_shapes(dict(cfg, num_classes=num_classes)), num_classes)
+        self.cfg = dict(cfg, num_classes=num_classes)
+        self.num_classes = num_classes
         self._bias_cache = {}
-        self._ws = {}
-        self._ws_used = []
-        self.kernel_events = None  # list: HIP events around each window-attention launch (bench.py)
-        self.concurrent_streams = None  # n > 1: the inference batch split over n HIP streams
-        self.split_sizes = None  # clips per stream part (streams.run_split); None = as even as possible
-        self._streams = None
-        self._split_out = {}
-        # True: the inference forward is captured once per input / configuration into a hipGraph and
-        # replayed (streams.GraphReplay); bit-identical logits
-        self.graph_replay = False
-        self._graphs = None
-        self._explain_ws = {}  # explain()'s own buffers per (B, geometry, device): not in _ws, which captured graphs hold on to
+        # kernel_events: a list collects HIP events around each window-attention launch (bench.py)
         self.stochastic_depth = True  # train step: torchvision's StochasticDepth on the residual branches
 
-    def state_dict(self, *a, **k):
-        return OrderedDict((n, self.params[n.replace(".", "__")].detach()) for n in self._names)
+    def _clean_state_dict(self, sd):  # relative_position_index: buffers, rebuilt
+        return {k: v for k, v in super()._clean_state_dict(sd).items() if not k.endswith("relative_position_index")}
 
-    def load_state_dict(self, sd, strict: bool = True):
-        sd = {k[len("module."):] if k.startswith("module.") else k: v for k, v in sd.items()}
-        sd = {k: v for k, v in sd.items() if not k.endswith("relative_position_index")}  # buffers, rebuilt
-        missing = [n for n in self._names if n not in sd]
-        unexpected = [k for k in sd if k not in self._names]
-        if strict and (missing or unexpected):
-            raise KeyError(f"load_state_dict: missing={missing[:5]} unexpected={unexpected[:5]}")
-        with torch.no_grad():
-            for n in self._names:
-                if n in sd:
-                    v = sd[n]
-                    v = torch.as_tensor(np.asarray(v)) if not isinstance(v, torch.Tensor) else v
-                    dst = self.params[n.replace(".", "__")]
-                    dst.copy_(v.reshape(dst.shape))
+    def _weights_replaced(self):
         self._packed = None
         self._bias_cache = {}
-        return missing, unexpected
 
     # ---- packing -------------------------------------------------------------------
-    def P(self, name):
-        return self.params[name.replace(".", "__")]
-
-    def _weights_version(self):
-        from . import vivit_train
-        return (vivit_train.MASTER_EPOCH[0], sum(p._version for p in self.params.values()))
-
     def _pack(self, device):
-        ver = self._weights_version()  # the fused AdamW updates in place without bumping _version
-        if self._packed is not None and self._packed["device"] == device and self._packed["version"] == ver:
-            return self._packed
+        pk = self._cached_pack(device)
+        if pk is not None:
+            return pk
         self._bias_cache = {}
         c = self.cfg
         bf, f32 = torch.bfloat16, torch.float32
@@ -241,7 +198,7 @@ class Swin3d(torch.nn.Module):
                 out[:b.numel()] = b
             return out
 
-        pk = {"device": device, "version": ver}
+        pk = {"device": device, "version": self._weights_version()}
         C0 = c["embed_dim"]
         pt, ph, pw = c["patch_size"]
         K0 = 3 * pt * ph * pw
@@ -305,14 +262,10 @@ class Swin3d(torch.nn.Module):
         return g
 
     def _workspace(self, B, grids, device, part: int = 0):
-        key = (B, tuple(grids), str(device), part)
-        if key in self._ws:
-            ws = self._ws[key]
-            if not any(w is ws for w in self._ws_used):
-                self._ws_used.append(ws)
-            return ws
-        if len(self._ws) >= 8:
-            self._ws = {}
+        return self._cached_workspace((B, tuple(grids), str(device), part),
+                                      lambda: self._make_workspace(B, grids, device), 8)
+
+    def _make_workspace(self, B, grids, device):
         c = self.cfg
         bf, f32 = torch.bfloat16, torch.float32
         z = lambda r, cols, dt=bf: torch.zeros((r, cols), dtype=dt, device=device)  # noqa: E731
@@ -332,8 +285,6 @@ class Swin3d(torch.nn.Module):
             ws["stages"].append(st)
         ws["logits"] = torch.zeros((B, self.num_classes), dtype=f32, device=device)
         ws["pool_work"] = torch.zeros(B * 64 * c["embed_dim"] * 2 ** (len(grids) - 1), dtype=f32, device=device)
-        self._ws[key] = ws
-        self._ws_used.append(ws)
         return ws
 
     # ---- forward -------------------------------------------------------------------
@@ -416,32 +367,14 @@ class Swin3d(torch.nn.Module):
         return A.pool_head(x, self.P("norm.weight"), self.P("norm.bias"), self.P("head.weight"), self.P("head.bias"), B,
                            t * h * w, eps)
 
-    def forward_logits(self, video: torch.Tensor) -> torch.Tensor:
-        """logits f32 [B, classes] (a workspace buffer, overwritten by the next call); with
-        `concurrent_streams = n > 1` the batch is split over n HIP streams (vclip_amd.streams):
-        one part's small late-stage launches run beside another part's early stages."""
-        B, Cin = video.shape[0], video.shape[1]
-        if Cin != 3:
+    # forward_logits (hosting.FusedVideoModel): under the stream split one part's small late-stage launches run
+    # beside another part's early stages
+    def _check_input(self, video):
+        if video.shape[1] != 3:
             raise ValueError("video must be [B, 3, T, H, W]")
-        if (self.graph_replay and self.kernel_events is None and not streams.serial()
-                and not torch.cuda.is_current_stream_capturing()):
-            from .streams import GraphReplay
-            if self._graphs is None:
-                self._graphs = GraphReplay()
-            key = (video.data_ptr(), tuple(video.shape), tuple(video.stride()), video.dtype, self.concurrent_streams, None if self.split_sizes is None else tuple(self.split_sizes),
-                   str(video.device), self._weights_version())
-            return self._graphs.run(key, video, self._forward_eager,
-                                    keep=lambda: (self._packed, tuple(self._ws_used), self._bias_cache))
-        return self._forward_eager(video)
 
-    def _forward_eager(self, video: torch.Tensor) -> torch.Tensor:
-        self._ws_used = []  # the workspaces this forward addresses (a captured graph keeps exactly these)
-        B = video.shape[0]
-        ns = max(1, min(int(self.concurrent_streams or 1), B))
-        if ns == 1:
-            return self._forward_part(video, 0)
-        from .streams import run_split
-        return run_split(self, video, ns, self._forward_part, self.num_classes, prepare=lambda: self._prepare(video))
+    def _graph_keep(self):
+        return super()._graph_keep() + (self._bias_cache,)
 
     def _prepare(self, video: torch.Tensor):
         """Packed weights and every block's bias operand for this clip geometry, built on the current

@@ -24,13 +24,12 @@ from __future__ import annotations
 
 import json
 import math
-from collections import OrderedDict
 
-import numpy as np
 import torch
 
-from . import ops, streams
-from .vivit import ClassifierOutput, _round_up
+from . import ops
+from .hosting import FusedVideoModel, round_up
+from .vivit import ClassifierOutput
 from .weights import timesformer_param_shapes
 
 
@@ -82,24 +81,19 @@ class TimesformerConfig:
         return f"TimesformerConfig({json.dumps(self.to_dict())})"
 
 
-class TimesformerForVideoClassification(torch.nn.Module):
+class TimesformerForVideoClassification(FusedVideoModel):
     """fp32 master parameters in HF naming (state_dict compatible with transformers'
     `TimesformerForVideoClassification`), bf16/fp32 packed device copies for the kernels."""
 
     def __init__(self, config: TimesformerConfig):
-        super().__init__()
-        self.config = config
         c = config
         if c.hidden_size // c.num_attention_heads != 64:
             raise ValueError("libvclip attention supports head_dim 64 only")
         if c.attention_type != "divided_space_time":
             raise ValueError("only attention_type='divided_space_time' (the reference's K400 checkpoint) is built")
-        self.params = torch.nn.ParameterDict()
-        shapes = timesformer_param_shapes(c.as_shape_cfg())
-        self._names = list(shapes.keys())
-        self.kernel_events = None  # list: HIP events around each spatial-attention launch (bench.py)
-        self.concurrent_streams = None  # n > 1: the inference batch split over n HIP streams
-        self.split_sizes = None  # clips per stream part (streams.run_split); None = as even as possible
+        super().__init__(timesformer_param_shapes(c.as_shape_cfg()), c.num_labels)
+        self.config = config
+        # kernel_events: a list collects HIP events around each spatial-attention launch (bench.py)
         # tile config of the two 768 x 768 bf16-output projections per layer (temporal dense, spatial
         # output): the 128x128 kernel (cfg 5), not vc_gemm's pick (the persistent 256x256 kernel,
         # 297 tiles = 1.16 rounds of 256 CUs at B=16): 37.9 vs 46.9 us at M = 25344 and 24.7 vs 25.4
@@ -107,55 +101,17 @@ class TimesformerForVideoClassification(torch.nn.Module):
         self.proj_cfg = 5
         # per-GEMM tile config overrides {"qkv_temporal" | "qkv_spatial" | "fc1" | "fc2": cfg} (A/B hook)
         self.gemm_cfg = {}
-        self._streams = None
-        self._split_out = {}
-        # True: the inference forward is captured once per input / configuration into a hipGraph and
-        # replayed (streams.GraphReplay); bit-identical logits
-        self.graph_replay = False
-        self._graphs = None
-        for name, shape in shapes.items():
-            self.params[name.replace(".", "__")] = torch.nn.Parameter(torch.zeros(shape))
-        self._packed = None
-        self._ws = {}
-        self._ws_used = []
-        self._explain_ws = {}  # explain()'s own buffers per (B, device): not in _ws, which captured graphs hold on to
-
-    def state_dict(self, *a, **k):
-        return OrderedDict((n, self.params[n.replace(".", "__")].detach()) for n in self._names)
-
-    def load_state_dict(self, sd, strict: bool = True):
-        sd = {k[len("module."):] if k.startswith("module.") else k: v for k, v in sd.items()}
-        missing = [n for n in self._names if n not in sd]
-        unexpected = [k for k in sd if k not in self._names]
-        if strict and (missing or unexpected):
-            raise KeyError(f"load_state_dict: missing={missing[:5]} unexpected={unexpected[:5]}")
-        with torch.no_grad():
-            for n in self._names:
-                if n in sd:
-                    v = sd[n]
-                    v = torch.as_tensor(np.asarray(v)) if not isinstance(v, torch.Tensor) else v
-                    dst = self.params[n.replace(".", "__")]
-                    dst.copy_(v.reshape(dst.shape))
-        self._packed = None
-        return missing, unexpected
-
-    def P(self, name):
-        return self.params[name.replace(".", "__")]
-
-    def _weights_version(self):
-        from . import vivit_train
-        return (vivit_train.MASTER_EPOCH[0], sum(p._version for p in self.params.values()))
 
     def _pack(self, device):
-        ver = self._weights_version()  # the fused AdamW updates in place without bumping _version
-        if self._packed is not None and self._packed["device"] == device and self._packed["version"] == ver:
-            return self._packed
+        pk = self._cached_pack(device)
+        if pk is not None:
+            return pk
         c = self.config
         bf, f32 = torch.bfloat16, torch.float32
         P = lambda n: self.P(n).detach().to(device=device, dtype=f32)  # noqa: E731
         D, T = c.hidden_size, c.num_frames
         e = "timesformer.embeddings."
-        pk = {"device": device, "version": ver}
+        pk = {"device": device, "version": self._weights_version()}
         pk["w_emb"] = P(e + "patch_embeddings.projection.weight").reshape(D, -1).to(bf).contiguous()
         pk["b_emb"] = P(e + "patch_embeddings.projection.bias").contiguous()
         pos = P(e + "position_embeddings").reshape(-1, D)
@@ -206,19 +162,14 @@ class TimesformerForVideoClassification(torch.nn.Module):
         P = (c.image_size // c.patch_size) ** 2
         T = c.num_frames
         S = 1 + P * T
-        Mpad = _round_up(max(B * S, B * T * (1 + P)) + 128, 256)
-        Memb = _round_up(B * P * T, 128)
+        Mpad = round_up(max(B * S, B * T * (1 + P)) + 128, 256)
+        Memb = round_up(B * P * T, 128)
         return P, T, S, Mpad, Memb
 
     def _workspace(self, B, device, part: int = 0):
-        key = (B, str(device), part)
-        if key in self._ws:
-            ws = self._ws[key]
-            if not any(w is ws for w in self._ws_used):
-                self._ws_used.append(ws)
-            return ws
-        if len(self._ws) >= 8:
-            self._ws = {}
+        return self._cached_workspace((B, str(device), part), lambda: self._make_workspace(B, device), 8)
+
+    def _make_workspace(self, B, device):
         c = self.config
         D, I = c.hidden_size, c.intermediate_size
         P, T, S, Mpad, Memb = self.geometry(B)
@@ -227,8 +178,6 @@ class TimesformerForVideoClassification(torch.nn.Module):
         ws = dict(A_emb=z(Memb, c.num_channels * c.patch_size * c.patch_size), X=z(Mpad, D, dt=torch.float32),
                   Hc=z(Mpad, D), Hf=z(Mpad, D), QKV=z(Mpad, 3 * D), O=z(Mpad, D), Yb=z(Mpad, D), Hd=z(Mpad, I),
                   logits=z(B, c.num_labels, dt=torch.float32))
-        self._ws[key] = ws
-        self._ws_used.append(ws)
         return ws
 
     def forward(self, pixel_values: torch.Tensor = None, labels: torch.Tensor = None, **kw):
@@ -250,35 +199,15 @@ class TimesformerForVideoClassification(torch.nn.Module):
             loss = torch.nn.functional.cross_entropy(logits, labels.to(logits.device))
         return ClassifierOutput(logits, loss)
 
-    def forward_logits(self, pix: torch.Tensor) -> torch.Tensor:
-        """logits f32 [B, labels] (a workspace buffer, overwritten by the next call); with
-        `concurrent_streams = n > 1` the batch is split over n HIP streams (vclip_amd.streams)."""
+    def _check_input(self, pix):
         c = self.config
         B, T, C, H, W = pix.shape
         if T != c.num_frames or H != c.image_size or W != c.image_size or C != c.num_channels:
             raise ValueError(f"pixel_values {tuple(pix.shape)} do not match config "
                              f"(T={c.num_frames}, C={c.num_channels}, {c.image_size}^2)")
-        if (self.graph_replay and self.kernel_events is None and not streams.serial()
-                and not torch.cuda.is_current_stream_capturing()):
-            from .streams import GraphReplay
-            if self._graphs is None:
-                self._graphs = GraphReplay()
-            key = (pix.data_ptr(), tuple(pix.shape), tuple(pix.stride()), pix.dtype, self.concurrent_streams, None if self.split_sizes is None else tuple(self.split_sizes), self.proj_cfg,
-                   tuple(sorted(self.gemm_cfg.items())),
-                   str(pix.device), self._weights_version())
-            return self._graphs.run(key, pix, self._forward_eager,
-                                    keep=lambda: (self._packed, tuple(self._ws_used)))
-        return self._forward_eager(pix)
 
-    def _forward_eager(self, pix: torch.Tensor) -> torch.Tensor:
-        self._ws_used = []  # the workspaces this forward addresses (a captured graph keeps exactly these)
-        c = self.config
-        B = pix.shape[0]
-        ns = max(1, min(int(self.concurrent_streams or 1), B))
-        if ns == 1:
-            return self._forward_part(pix, 0)
-        from .streams import run_split
-        return run_split(self, pix, ns, self._forward_part, c.num_labels, prepare=lambda: self._pack(pix.device))
+    def _graph_knobs(self):
+        return (self.proj_cfg, tuple(sorted(self.gemm_cfg.items())))
 
     def _forward_part(self, pix: torch.Tensor, part: int, out=None, keep=None) -> torch.Tensor:
         """keep (explain only): {"QKV_t": [L, Mpad, 3D], "QKV_s": [L, Mpad, 3D], "LSE_s": [L, B*T*H*(1+P)]} -- layer
@@ -456,7 +385,7 @@ class TimesformerForVideoClassification(torch.nn.Module):
         S = 1 + P * T
         e = "timesformer.embeddings."
         M = B * P * T
-        a_emb = torch.zeros(_round_up(M, 128), C * pc * pc, dtype=torch.bfloat16, device=pix.device)
+        a_emb = torch.zeros(round_up(M, 128), C * pc * pc, dtype=torch.bfloat16, device=pix.device)
         ops.tubelet_im2col(pix, (1, pc, pc), a_emb, order="patch_major")  # rows (b, p, t)
         emb = A.linear(a_emb[:M], self.P(e + "patch_embeddings.projection.weight").reshape(D, -1),
                        self.P(e + "patch_embeddings.projection.bias"), out_f32=True)

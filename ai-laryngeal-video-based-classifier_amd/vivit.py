@@ -26,8 +26,8 @@ from collections import OrderedDict
 import numpy as np
 import torch
 
-from . import ops, streams
-from .streams import GraphReplay
+from . import ops
+from .hosting import FusedVideoModel, round_up
 from .vivit_explain import GradRolloutEngine
 from .vivit_train import FlatLayout, TrainEngine, VivitTrainFn
 from .weights import vivit_param_shapes
@@ -114,25 +114,17 @@ class ClassifierOutput:
 SPLIT_DEFAULT = {(8, 2): (5, 3)}
 
 
-def _round_up(x, m):
-    return (x + m - 1) // m * m
-
-
-class VivitForVideoClassification(torch.nn.Module):
+class VivitForVideoClassification(FusedVideoModel):
     """fp32 master parameters in HF naming (state_dict compatible with transformers-5
     `VivitForVideoClassification`), bf16/fp32 packed device copies for the kernels."""
 
     def __init__(self, config: VivitConfig):
-        super().__init__()
-        self.config = config
         c = config
         if c.hidden_size // c.num_attention_heads != 64:
             raise ValueError("libvclip attention supports head_dim 64 only")
-        self.params = torch.nn.ParameterDict()
         shapes = vivit_param_shapes(c.as_shape_cfg())
-        self._names = list(shapes.keys())
-        for name, shape in shapes.items():
-            self.params[name.replace(".", "__")] = torch.nn.Parameter(torch.zeros(shape))
+        super().__init__(shapes, c.num_labels)
+        self.config = config
         self._layout = FlatLayout(c, shapes)
         self._flat = None      # fp32 masters, one device buffer (params are views), built for training
         self._gflat = None     # gradients, same layout (p.grad are views)
@@ -140,25 +132,7 @@ class VivitForVideoClassification(torch.nn.Module):
         self._engine = None
         self._lora = None      # vclip_amd.lora.LoraState while adapters are attached (lora.attach)
         self.grad_ready_hooks = []  # fn(stage, start, end, gflat): a slice of gflat is final (enqueued)
-        self._packed = None
-        self._ws = {}
-        self._ws_used = []
-        self._explain_ws = {}  # explain()'s own buffers per (B, device): not in _ws, which captured graphs hold on to
         self._explain_grad = {}  # explain(method="grad_rollout")'s engine per (B, device) (vivit_explain.py)
-        self._streams = None
-        self.concurrent_streams = None  # None / 1: one stream; n > 1: batch split over n HIP streams
-        # HIP stream priority per part (lower is higher) of the eager forward's part streams, an A/B hook;
-        # None: the stream set streams.part_streams timed fastest on the first call.  Under graph replay
-        # the part graphs run on the set streams.GraphReplay._tune timed fastest; profiles/r06_hwq.txt
-        self.stream_priorities = None
-        # clips per stream part (A/B hook; must sum to the batch): None = as even as possible
-        self.split_sizes = None
-        self.last_streams = 1
-        self.kernel_events = None
-        # True: the inference forward is captured once per input / configuration into a hipGraph
-        # and replayed (streams.GraphReplay); bit-identical logits
-        self.graph_replay = False
-        self._graphs = GraphReplay()
         # per-GEMM tile config override {"qkv" | "o_proj" | "fc1" | "fc2": vc_gemm cfg} (None / absent:
         # vc_gemm's own pick) and the GEMM / LayerNorm row count: "pad" = every padded row (Mpad),
         # "tight" = B*S rounded up to the tile height (the padding rows keep their initial zeros)
@@ -189,42 +163,17 @@ class VivitForVideoClassification(torch.nn.Module):
     def hf_state_dict(self):
         return OrderedDict((n, self.params[n.replace(".", "__")]) for n in self._names)
 
-    def state_dict(self, *a, **k):  # noqa: D401 - HF key names, like the reference's model
-        return OrderedDict((n, p.detach()) for n, p in self.hf_state_dict().items())
-
-    def load_state_dict(self, sd, strict: bool = True):
+    def _clean_state_dict(self, sd):
         from .checkpoint import convert_state_dict
-        sd = convert_state_dict(sd)
-        missing = [n for n in self._names if n not in sd]
-        unexpected = [k for k in sd if k not in self._names]
-        if strict and (missing or unexpected):
-            raise KeyError(f"load_state_dict: missing={missing[:5]} unexpected={unexpected[:5]}")
-        with torch.no_grad():
-            for n in self._names:
-                if n in sd:
-                    v = sd[n]
-                    v = torch.as_tensor(np.asarray(v)) if not isinstance(v, torch.Tensor) else v
-                    self.params[n.replace(".", "__")].copy_(v.reshape(self.params[n.replace(".", "__")].shape))
-        self._packed = None
-        return missing, unexpected
-
-    def P(self, name):
-        return self.params[name.replace(".", "__")]
-
-    def _param_list(self):
-        return [self.P(n) for n in self._names]
+        return convert_state_dict(sd)
 
     def _apply(self, fn, *args, **kwargs):  # .to() / .cuda(): parameters move one by one
         out = super()._apply(fn, *args, **kwargs)
         self._flat = self._gflat = self._gscratch = self._engine = None
         if self._lora is not None:
             self._lora.reset()
-        self._packed = None
-        self._ws = {}
-        self._explain_ws = {}
         self._explain_grad = {}
-        self._streams = None
-        self._graphs.clear()
+        self._drop_device_state()
         return out
 
     # ---- training (vclip_amd/vivit_train.py) --------------------------
@@ -307,15 +256,13 @@ class VivitForVideoClassification(torch.nn.Module):
                 h(stage, start, end, self._gflat)
 
     def _weights_version(self):
-        from . import vivit_train
-        ver = (vivit_train.MASTER_EPOCH[0], sum(p._version for p in self._param_list()))
+        ver = super()._weights_version()
         if self._lora is not None:  # the adapters are part of the weights the packs are made from
             ver += (id(self._lora), sum(p._version for p in self._lora.params(self)))
         return ver
 
     # ---- device packing ----------------------------------------------------------
     def _pack(self, device):
-        ver = self._weights_version()
         bf = self.compute_dtype
         if bf not in (torch.bfloat16, torch.float16):
             raise ValueError(f"compute_dtype must be torch.bfloat16 or torch.float16, not {bf}")
@@ -323,9 +270,9 @@ class VivitForVideoClassification(torch.nn.Module):
         pops = tuple(sorted(self.precise_ops)) if npre > 0 else ()
         if not set(pops) <= {"embed", "embed_w", "qkv", "o_proj", "fc1", "fc2"} or {"embed", "embed_w"} <= set(pops):
             raise ValueError(f"precise_ops must name embed | embed_w and q|k|v / o_proj / fc1 / fc2, not {self.precise_ops}")
-        if (self._packed is not None and self._packed["device"] == device and self._packed["version"] == ver
-                and self._packed["dtype"] == bf and self._packed["precise"] == npre and self._packed["pops"] == pops):
-            return self._packed
+        pk = self._cached_pack(device, (bf, npre, pops))
+        if pk is not None:
+            return pk
         c = self.config
         f32 = torch.float32
         P = lambda n: self.P(n).detach().to(device)  # noqa: E731
@@ -340,7 +287,7 @@ class VivitForVideoClassification(torch.nn.Module):
                            else self.P(n).detach().to(device))
         D = c.hidden_size
         kt, kh, kw = c.tubelet_size
-        pk = {"device": device, "version": ver, "dtype": bf, "precise": npre, "pops": pops}
+        pk = {"device": device, "version": self._weights_version(), "extra": (bf, npre, pops), "pops": pops}
 
         def split(w, emb=False):
             # [W_hi | W_lo] (embedding: [W_hi | W_hi | W_lo] against [A_hi | A_lo] with A wrapping)
@@ -403,19 +350,16 @@ class VivitForVideoClassification(torch.nn.Module):
         kt, kh, kw = c.tubelet_size
         npatch = (c.num_frames // kt) * (c.image_size // kh) * (c.image_size // kw)
         S = npatch + 1
-        Mpad = _round_up(B * S + 128, 256)
-        Memb = _round_up(B * npatch, 128)
+        Mpad = round_up(B * S + 128, 256)
+        Memb = round_up(B * npatch, 128)
         return npatch, S, Mpad, Memb
 
     def _workspace(self, B, device, part: int = 0):
-        key = (B, str(device), part, self.compute_dtype, self.precise_layers > 0)
-        if key in self._ws:
-            ws = self._ws[key]
-            if not any(w is ws for w in self._ws_used):
-                self._ws_used.append(ws)
-            return ws
-        if len(self._ws) >= 8:  # (1 + 2 stream parts) x {bf16, fp16} + the split logits fit
-            self._ws = {}
+        # 8 entries: (1 + 2 stream parts) x {bf16, fp16} fit
+        return self._cached_workspace((B, str(device), part, self.compute_dtype, self.precise_layers > 0),
+                                      lambda: self._make_workspace(B, device), 8)
+
+    def _make_workspace(self, B, device):
         c = self.config
         D, I = c.hidden_size, c.intermediate_size
         kt, kh, kw = c.tubelet_size
@@ -429,7 +373,7 @@ class VivitForVideoClassification(torch.nn.Module):
             # rounded up to 256 (zero rows past B*npatch), and X 256 rows deeper so the remapped rows of that
             # padding (tokens B*S+1 .. B*S+256, values bias + pos: finite) stay inside the buffer; the layers
             # address X[:Mpad] as always
-            Memb = _round_up(B * npatch, 256)
+            Memb = round_up(B * npatch, 256)
             Xe = z(Mpad + 256, D, dt=torch.float32)
         else:
             Xe = z(Mpad, D, dt=torch.float32)
@@ -439,8 +383,6 @@ class VivitForVideoClassification(torch.nn.Module):
                   cls_work=ops.cls_attention_work(B, S, c.num_attention_heads, device), Hc=z(B, I))
         if precise:
             ws["A_emb_split"] = z(Memb, 2 * Kemb)
-        self._ws[key] = ws
-        self._ws_used.append(ws)
         return ws
 
     # ---- forward -----------------------------------------------------------------
@@ -464,82 +406,34 @@ class VivitForVideoClassification(torch.nn.Module):
             loss = torch.nn.functional.cross_entropy(logits, labels.to(logits.device))
         return ClassifierOutput(logits, loss)
 
-    @torch.no_grad()
-    def forward_logits(self, pix: torch.Tensor) -> torch.Tensor:
-        """logits f32 [B, labels] (a workspace buffer, overwritten by the next call).
-
-        `concurrent_streams = n > 1` splits the batch over n HIP streams, each part with its own
-        workspace, so one part's kernels fill the CUs another part's tail rounds and short launches
-        leave idle: ViViT-B B = 8 840 -> 916 and 857 -> 911 clips/s with 2 streams on two boxes
-        (tools/exp_streams.py; 3 streams 813-855).  bench.py's headline runs 2 streams; its kernel
-        roofline is timed in a separate one-stream pass (under overlap a launch's event time
-        includes time shared with the other stream's kernels).  Logits are bit-identical either
-        way (every kernel is batch-invariant)."""
+    def _check_input(self, pix):
         c = self.config
         B, T, C, H, W = pix.shape
         if T != c.num_frames or H != c.image_size or W != c.image_size or C != c.num_channels:
             raise ValueError(f"pixel_values {tuple(pix.shape)} do not match config "
                              f"(T={c.num_frames}, C={c.num_channels}, {c.image_size}^2)")
-        if (self.graph_replay and self.kernel_events is None and not streams.serial()
-                and not torch.cuda.is_current_stream_capturing()):
-            key = (pix.data_ptr(), tuple(pix.shape), tuple(pix.stride()), pix.dtype, self.concurrent_streams,
-                   self.compute_dtype, self._weights_version(),
-                   tuple(sorted((k, tuple(v) if isinstance(v, list) else v) for k, v in self.gemm_cfg.items())), self.rows,
-                   self.precise_layers, tuple(sorted(self.precise_ops)),
-                   None if self.split_sizes is None else tuple(self.split_sizes),
-                   None if self.stream_priorities is None else tuple(self.stream_priorities),
-                   self._cls_only())
-            return self._graphs.run(key, pix, self._forward_eager, keep=lambda: (self._packed, tuple(self._ws_used)))
-        return self._forward_eager(pix)
+
+    # forward_logits (hosting.FusedVideoModel): with `concurrent_streams = n > 1` one part's kernels fill the
+    # CUs another part's tail rounds and short launches leave idle: ViViT-B B = 8 840 -> 916 and 857 -> 911
+    # clips/s with 2 streams on two boxes (tools/exp_streams.py; 3 streams 813-855).  bench.py's headline runs
+    # 2 streams; its kernel roofline is timed in a separate one-stream pass (under overlap a launch's event
+    # time includes time shared with the other stream's kernels).
+    def _graph_knobs(self):
+        return (self.compute_dtype,
+                tuple(sorted((k, tuple(v) if isinstance(v, list) else v) for k, v in self.gemm_cfg.items())), self.rows,
+                self.precise_layers, tuple(sorted(self.precise_ops)),
+                None if self.stream_priorities is None else tuple(self.stream_priorities), self._cls_only())
 
     def _cls_only(self) -> bool:
         return bool(self.cls_only_last_layer) and not self.training
 
-    def _forward_eager(self, pix: torch.Tensor) -> torch.Tensor:
-        self._ws_used = []  # the workspaces this forward addresses (a captured graph keeps exactly these)
-        c = self.config
-        B = pix.shape[0]
-        ns = self.concurrent_streams or 1
-        ns = max(1, min(int(ns), B))
-        self.last_streams = ns
-        if ns == 1:
-            self.last_split = [B]
-            return self._forward_part(pix, 0, cls_only=self._cls_only())
-        dev = pix.device
-        key = (B, str(dev), "logits")
-        if key not in self._ws:
-            self._ws[key] = torch.zeros(B, c.num_labels, dtype=torch.float32, device=dev)
-        logits = self._ws[key]
-        cur = torch.cuda.current_stream(dev)
-        # the packed weights every part reads are built on the caller's stream before the fork
-        # (streams.run_split's rule): packed inside part 0 they would race parts 1..n-1
-        self._pack(dev)
-        bounds = streams.split_bounds(B, ns, self.split_sizes if self.split_sizes is not None
-                                      else SPLIT_DEFAULT.get((B, ns)))
-        self.last_split = [bounds[i + 1] - bounds[i] for i in range(ns)]
-        cls_only = self._cls_only()
-        if streams.serial():  # instrumentation: the parts one after the other on the caller's stream
-            for i in range(ns):
-                self._forward_part(pix[bounds[i]:bounds[i + 1]], i, out=logits[bounds[i]:bounds[i + 1]],
-                                   cls_only=cls_only)
-            return logits
-        # whole parts enqueued one after the other (measured, tools/exp_streams.py: enqueueing the
-        # parts layer by layer round robin ran 725 vs 911 clips/s, chaining their attention launches
-        # across the streams 721, and starting part i+1 at a fixed op of part i's first layer 887-906)
-        def go(sts):
-            for st in sts:
-                pix.record_stream(st)
-            streams.fork_parts(sts, cur, [lambda i=i: self._forward_part(pix[bounds[i]:bounds[i + 1]], i,
-                                                                          out=logits[bounds[i]:bounds[i + 1]],
-                                                                          cls_only=cls_only)
-                                          for i in range(ns)])
+    def _part_kwargs(self):
+        return dict(cls_only=self._cls_only())
 
-        # the parts' streams: on different hardware queues, the fastest of several sets timed on the first
-        # call per configuration (streams.part_streams)
-        self._streams = streams.part_streams(self, (B, ns, str(dev), tuple(bounds), self.compute_dtype), ns, go,
-                                             dev, self.stream_priorities)
-        go(self._streams)
-        return logits
+    def _split_options(self, B, ns):
+        # the tuning of the part streams is per operand type too
+        return dict(sizes=self.split_sizes if self.split_sizes is not None else SPLIT_DEFAULT.get((B, ns)),
+                    key_extra=(self.compute_dtype,))
 
     def _forward_part(self, pix: torch.Tensor, part: int, out=None, cls_only: bool = False, keep=None) -> torch.Tensor:
         """One part's forward.  cls_only = False: every layer over every token row (X ends as the full last
@@ -613,7 +507,7 @@ class VivitForVideoClassification(torch.nn.Module):
             if not tight:
                 return None, -1 if cfg is None else cfg
             h = 128 if cfg in (5, 7, 21) else 256
-            return _round_up(B * S, h), -1 if cfg is None else cfg
+            return round_up(B * S, h), -1 if cfg is None else cfg
 
         m_ln = B * S if tight else None
         (m_qkv, c_qkv), (m_o, c_o), (m_1, c_1), (m_2, c_2) = rows("qkv"), rows("o_proj"), rows("fc1"), rows("fc2")

@@ -25,16 +25,13 @@ import math
 import torch
 
 from . import ops, streams
+from .hosting import round_up as _round_up
 
 ALIGN = 64
 
 # bumped by vclip_amd.optim.AdamW after it rewrites fp32 masters through raw pointers (no torch
 # version-counter bump), so inference-side bf16 packs know to refresh
 MASTER_EPOCH = [0]
-
-
-def _round_up(x, m):
-    return (x + m - 1) // m * m
 
 
 def flat_order(cfg) -> list:

@@ -107,6 +107,25 @@ def test_vivit_two_stream_split_bit_exact():
         m.forward_logits(pix)
 
 
+def test_vivit_split_without_a_default_table_entry():
+    """B = 3 on two streams: vivit.SPLIT_DEFAULT has no (3, 2) entry, so the split is the even one, 1 + 2;
+    model.split_sizes overrides it.  Either way the logits are the one-stream logits bit for bit, in the
+    model's split-logits buffer (streams.run_split)."""
+    g = np.load(os.path.join(GD, "vivit_tiny.npz"))
+    m = _model(json.loads(str(g["config"])))
+    pix = torch.from_numpy(g["pixel_values"]).cuda()
+    pix3 = torch.cat([pix, pix[:1]])[:3].contiguous()
+    one = m.forward_logits(pix3).clone()
+    assert m.last_streams == 1 and m.last_split == [3]
+    m.concurrent_streams = 2
+    for sizes, want in ((None, [1, 2]), ([2, 1], [2, 1])):
+        m.split_sizes = sizes
+        got = m.forward_logits(pix3)
+        assert m.last_streams == 2 and m.last_split == want
+        assert got is m._split_out[(3, "cuda:0", "split_logits")]
+        assert torch.equal(got, one), sizes
+
+
 def test_vivit_tiny_per_layer_drift():
     """Hidden-state drift layer by layer against the HF golden (tests/golden/vivit_tiny.npz holds the
     embeddings output and every layer's output): the GPU forward is run with its first k layers and
