@@ -5,7 +5,8 @@
 //    (TimesformerSelfAttention over the T frames of one patch, TF5/models/timesformer/
 //    modeling_timesformer.py:148-180 as called from :332-349): per (sequence, head) the T x T
 //    scores are recomputed from q' (= q * scale * log2 e, the stored q|k|v layout of the forward),
-//    P = softmax, dV = P^T dO, dP = dO V^T, dS = ln2 * P o (dP - rowsum(P o dP)),
+//    P = softmax, dV = P^T dO, dP = dO V^T, dS = ln2 * P o (dP - rowsum(P o dP)) (the entry of the
+//    row's largest score as minus the sum of the others: rows of dS sum to zero),
 //    dQ' = dS K, dK = dS^T Q'.  T <= 32 keys: VALU work, one wave per (sequence, head), the rows and
 //    the T x T tiles in LDS, every lane busy in every phase.  Deterministic (no atomics).
 //  * gelu_erf_fwd_kernel / gelu_erf_bwd_kernel — exact GELU (TimeSformer / Swin hidden_act
@@ -82,7 +83,12 @@ __global__ void __launch_bounds__(64) temporal_attn_bwd_kernel(const uint16_t* _
 
     if (l < T) {
         float m = -INFINITY;
-        for (int u = 0; u < T; ++u) m = fmaxf(m, sP[l][u]);
+        int um = 0;  // the row's largest score
+        for (int u = 0; u < T; ++u)
+            if (sP[l][u] > m) {
+                m = sP[l][u];
+                um = u;
+            }
         float sum = 0.f;
         for (int u = 0; u < T; ++u) {
             const float e = exp2f(sP[l][u] - m);
@@ -96,7 +102,16 @@ __global__ void __launch_bounds__(64) temporal_attn_bwd_kernel(const uint16_t* _
             sP[l][u] = p;
             delta = __builtin_fmaf(p, sD[l][u], delta);
         }
-        for (int u = 0; u < T; ++u) sD[l][u] = LN2 * sP[l][u] * (sD[l][u] - delta);
+        // A row of dS sums to zero.  Where one key holds nearly all of P, delta rounds to that key's
+        // dP and the direct form gives it dS = 0, losing the row's whole gradient (the other entries
+        // are of the order of their tiny P); the largest entry is minus the sum of the others instead.
+        float rest = 0.f;
+        for (int u = 0; u < T; ++u) {
+            const float ds = LN2 * sP[l][u] * (sD[l][u] - delta);
+            sD[l][u] = ds;
+            if (u != um) rest += ds;
+        }
+        sD[l][um] = -rest;
     }
     __syncthreads();
 

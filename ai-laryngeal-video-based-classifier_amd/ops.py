@@ -929,7 +929,9 @@ def frame_avgpool_bwd(g: torch.Tensor, N: int, P: int, C: int, out: torch.Tensor
 
 def attention_fwd_lse(qkv: torch.Tensor, B: int, S: int, H: int, out: torch.Tensor, lse: torch.Tensor,
                       scale: float = 0.125, q_prescaled: bool = True) -> torch.Tensor:
-    """vc_attention_fwd that also stores the base-2 log-sum-exp lse f32 [B*H*S]."""
+    """vc_attention_fwd that also stores the base-2 log-sum-exp lse f32 [B*H*S].
+    The padding rows of qkv (past B*S, up to the last clip's 64-key tile) must hold finite values: they are
+    read and multiplied by zero, so a NaN or Inf there reaches valid rows."""
     _dev(qkv, out, lse)
     _need(lse.dtype == torch.float32 and lse.is_contiguous() and lse.numel() >= B * H * S, "lse: f32 [B*H*S]")
     _need(qkv.dtype == torch.bfloat16 and out.dtype == torch.bfloat16 and qkv.stride(1) == 1 and out.stride(1) == 1,
@@ -1066,7 +1068,9 @@ def attention_bwd(qkv: torch.Tensor, out: torch.Tensor, dout: torch.Tensor, lse:
                   B: int, S: int, H: int, dqkv: torch.Tensor, stream2: torch.cuda.Stream | None = None) -> torch.Tensor:
     """dqkv (q part = dL/dq' of the stored pre-scaled q', then dk, dv) of the joint attention.
     `stream2`: the dQ kernel runs there beside dK/dV (vc_attention_bwd_2s); the current stream waits
-    for it before anything enqueued after this call."""
+    for it before anything enqueued after this call.
+    The padding rows of qkv and dout (past B*S, up to the last clip's 64-row tile) must hold finite values:
+    they are read and multiplied by zero, so a NaN or Inf there reaches valid rows of dqkv."""
     _dev(qkv, out, dout, lse, delta, dqkv)
     for t, nm in ((qkv, "qkv"), (out, "out"), (dout, "dout"), (dqkv, "dqkv")):
         _need(t.dtype == torch.bfloat16 and t.stride(1) == 1, f"attention_bwd: {nm} bf16 with unit column stride")
