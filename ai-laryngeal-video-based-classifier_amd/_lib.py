@@ -124,6 +124,9 @@ SIGNATURES = {
     "vc_temporal_rollout_step": ([c_p, c_i64, c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_f, c_p, c_p, c_p], c_int),
     "vc_window_rollout_step": ([c_p, c_i64, c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_int, c_int, c_int,
                                 c_int, c_int, c_int, c_int, c_int, c_int, c_f, c_p, c_i64, c_p, c_p], c_int),
+    "vc_window_grad_rollout_step": ([c_p, c_i64, c_p, c_i64, c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64,
+                                     c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_f, c_f, c_p, c_i64,
+                                     c_p, c_p, c_p], c_int),
     "vc_merge_rollout_spread": ([c_p, c_i64, c_i64, c_i64, c_i64, c_p, c_p], c_int),
     "vc_attention_bwd": ([c_p, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_p, c_i64, c_p],
                          c_int),

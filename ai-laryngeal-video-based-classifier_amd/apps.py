@@ -234,7 +234,9 @@ SWIN_SALIENCY_HELP = (
     "absent (default): the label only, as the reference.  rollout: attention rollout from the pooled tokens back "
     "through every block's shifted-window attention and every PatchMerging (Swin3d.explain).  Writes "
     "<video>_saliency.npy (f32 [T/2, H/4, W/4], sums to 1) beside the result JSON, which gains a \"saliency\" object "
-    "with each time step's importance and the two source-frame indices it covers.")
+    "with each time step's importance and the two source-frame indices it covers.  class_rollout: the class-specific "
+    "gradient-weighted rollout (Chefer et al. 2021) through the same blocks (Swin3d.explain_class) for "
+    "--saliency_class; the \"saliency\" object then names target_class / target_label.")
 
 
 RESNET3D_SALIENCY_HELP = (
@@ -253,7 +255,7 @@ RISE_SALIENCY_HELP = (
     "score-weighted mean of --rise_masks smooth random masks, for --saliency_class; <video>_saliency.npy is then f32 "
     "[T, H, W] and the \"saliency\" object names masks, cells, keep and seed.")
 # per family: the --saliency methods that take --saliency_class
-CLASS_SPECIFIC_SALIENCY = {"vivit": ("grad_rollout", "rise"), "timesformer": ("rise",), "swin": ("rise",),
+CLASS_SPECIFIC_SALIENCY = {"vivit": ("grad_rollout", "rise"), "timesformer": ("rise",), "swin": ("rise", "class_rollout"),
                            "resnet3d": ("gradcam", "hirescam", "rise")}
 
 
@@ -295,7 +297,7 @@ def build_parser(fam: Family, inference: bool, saliency: bool = False):
     """The folder's reference flags (plus ViViT's --saliency / --saliency_class).  saliency=True, as run_inference
     builds it: the TimeSformer, Swin and ResNet3D inference parsers also get their own --saliency (ResNet3D's with
     --saliency_class and --saliency_layer), and all four the method `rise` with --rise_masks and --rise_seed (and
-    TimeSformer and Swin the --saliency_class that only `rise` takes); the two-argument form keeps the flag surface
+    TimeSformer and Swin the --saliency_class that only `rise` and Swin's `class_rollout` take); the two-argument form keeps the flag surface
     those families had before their `explain` existed."""
     if fam.name == "lstm":
         return build_parser_lstm(inference)
@@ -326,12 +328,13 @@ def build_parser(fam: Family, inference: bool, saliency: bool = False):
                                 "predicted class); the result JSON's \"saliency\" object names it as target_class / "
                                 "target_label")
         elif fam.name in ("timesformer", "swin") and saliency:
-            own = ["rollout", "cls_attention"] if fam.name == "timesformer" else ["rollout"]
+            own = ["rollout", "cls_attention"] if fam.name == "timesformer" else ["rollout", "class_rollout"]
             p.add_argument("--saliency", type=str, default=None, choices=own + rise,
                            help=(TIMESFORMER_SALIENCY_HELP if fam.name == "timesformer" else SWIN_SALIENCY_HELP) + more)
             p.add_argument("--saliency_class", type=int, default=None,
-                           help="with --saliency rise: the class index whose evidence is mapped (absent: the predicted "
-                                "class); the result JSON's \"saliency\" object names it as target_class / target_label")
+                           help=f"with --saliency {' or '.join(CLASS_SPECIFIC_SALIENCY[fam.name])}: the class index whose "
+                                "evidence is mapped (absent: the predicted class); the result JSON's \"saliency\" object "
+                                "names it as target_class / target_label")
             p.class_methods = CLASS_SPECIFIC_SALIENCY[fam.name]
         elif fam.name == "resnet3d" and saliency:
             p.add_argument("--saliency", type=str, default=None, choices=["gradcam", "hirescam"] + rise,
@@ -671,6 +674,8 @@ def run_inference(fam_name, argv=None):
         elif fam.name == "resnet3d":
             ex = model.explain(x, method=saliency, target=pred if saliency_class is None else saliency_class,
                                layer=args.saliency_layer)
+        elif saliency == "class_rollout":  # Swin's class-specific map: the asked class, or the label printed above
+            ex = model.explain_class(x, target=pred if saliency_class is None else saliency_class)
         elif saliency == "grad_rollout":  # class-specific: the asked class, or the label printed above
             ex = model.explain(x, method=saliency, target=pred if saliency_class is None else saliency_class)
         else:

@@ -116,15 +116,19 @@ class _Linear(torch.autograd.Function):
         dyp = _as_operand(dy, Mp, Np)
         dx = torch.empty(Mp, Kp, dtype=torch.bfloat16, device=dy.device)
         ops.gemm(dyp, wt, _zeros_f32(Kp, dy.device), "bias", dx)
-        dw = torch.empty(Np, Kp, dtype=torch.float32, device=dy.device)
-        ops.wgrad(dyp, xp, dw, ops.wgrad_work(Mp, Np, Kp, dy.device), nscaled=ctx.qrows, scale=ctx.qscale)
+        # a weight or bias that needs no gradient (a data-gradient chain on detached masters: Swin3d.explain_class)
+        # costs neither its wgrad GEMM nor its column sum; the train step needs both and runs as before
+        dw = None
+        if ctx.needs_input_grad[1]:
+            dw = torch.empty(Np, Kp, dtype=torch.float32, device=dy.device)
+            ops.wgrad(dyp, xp, dw, ops.wgrad_work(Mp, Np, Kp, dy.device), nscaled=ctx.qrows, scale=ctx.qscale)
+            dw = dw[:N, :K] if (Np, Kp) != (N, K) else dw
         db = None
-        if ctx.has_bias:
+        if ctx.has_bias and ctx.needs_input_grad[2]:
             db = torch.empty(Np, dtype=torch.float32, device=dy.device)
             ops.colsum(dyp, db, ops.colsum_work(M, Np, dy.device), m=M, nscaled=ctx.qrows, scale=ctx.qscale)
             db = db[:N]
         dx = dx[:M, :K] if Kp != K else dx[:M]
-        dw = dw[:N, :K] if (Np, Kp) != (N, K) else dw
         return dx.to(ctx.xdtype), dw, db, None, None, None
 
 
@@ -237,6 +241,8 @@ class _GeluErf(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
+        if not ctx.needs_input_grad[0]:  # for symmetry with the ops above: autograd never calls the backward of a
+            return None                  # one-input Function whose input needs no gradient, so this is not reached
         (x,) = ctx.saved_tensors
         M, N = x.shape
         dy = dy.contiguous()
@@ -310,6 +316,8 @@ class _WindowAttention(torch.autograd.Function):
         part = torch.empty(nwin, heads * ntab, dtype=torch.float32, device=qkv.device)
         tab = table.detach().float().contiguous()
         ops.window_attention3d_bwd(qkv, out, d, lse, B, grid, heads, window, shift, full_window, tab, dqkv, part)
+        if not ctx.needs_input_grad[1]:  # a frozen table: its per-window partials are not reduced
+            return dqkv, None, None, None, None, None, None, None
         dtab = torch.empty(heads * ntab, dtype=torch.float32, device=qkv.device)
         ops.colsum(part, dtab, ops.colsum_work(part.shape[0], dtab.numel(), part.device))  # fixed order
         return dqkv, dtab.view(heads, ntab).t(), None, None, None, None, None, None
@@ -357,7 +365,10 @@ class _PoolHead(torch.autograd.Function):
         nb = min(512, (M + 3) // 4)
         work = torch.empty((nb + (nb + 31) // 32) * 4 * D, dtype=torch.float32, device=x.device)
         ops.layernorm_bwd(dy, x, g, eps, dx, dxb, dg, db, work)
-        return dx, dg, db, dwc, dbc, None, None, None
+        # both kernels write the parameter gradients beside dx; only the ones asked for are handed on
+        need = ctx.needs_input_grad
+        return (dx, dg if need[1] else None, db if need[2] else None, dwc if need[3] else None,
+                dbc if need[4] else None, None, None, None)
 
 
 def pool_head(x, g, b, wc, bc, B, ntok, eps):

@@ -30,6 +30,14 @@
 //
 // vc_merge_rollout_spread is the hop through PatchMerging: a merged token gives an equal share of its relevance to
 // each of its existing children.
+//
+// vc_window_grad_rollout_step is the class-specific step (Chefer, Gur & Wolf 2021): the same three launches with the
+// probabilities weighted by the positive part of their gradient dP_h[i][j] = dO_h[i] . v_j,
+//     u[j] = (1/heads) sum_h sum_{i in win(j)} r_in[i] * P_h[i][j] * max(dP_h[i][j], 0),
+//     a_out[j] = alpha * u[j] + beta * a_in[j],   r_out[j] = a_out[j] + base[j].
+// The normaliser kernel is reused as it is; window_grad_rollout_cols_kernel is the column kernel with the window's dO
+// rows staged beside its q' rows and the lane's v row read beside its k row, so both 32x32 products land in the same
+// registers (72 KB of LDS at the full window: the kernel's dynamic-LDS limit is raised).
 #include "window_common.hpp"
 
 namespace vc {
@@ -303,6 +311,144 @@ static bool overlap(const float* a, int64_t na, const float* b, int64_t nb) {
     return a0 < b0 + (uintptr_t)nb * 4 && b0 < a0 + (uintptr_t)na * 4;
 }
 
+// ---- the gradient-weighted step (vc_window_grad_rollout_step) ------------------------------------------------------
+// The column kernel with a second product: beside the q' rows the window's dO rows are staged, and the lane's v row
+// is read beside its k row, so dP = dO . V^T lands in the registers S = Q' . K^T lands in.
+constexpr int64_t GLDS_MAX = 160 * 1024;  // the CU's LDS; above 64 KiB the kernel's dynamic-LDS limit is raised
+
+// LDS of the gradient column kernel: lds_bytes plus the dO rows [NP][64 B] (72 864 B at the full window)
+__host__ __device__ inline int64_t grad_lds_bytes(int64_t NP, int64_t ntab) { return lds_bytes(NP, ntab) + NP * 64; }
+
+// the window's rows of this head from a row-major bf16 matrix (zeros in the padded slots), stage's chunk swizzle
+__device__ __forceinline__ void stage_rows(const uint16_t* __restrict__ src, int64_t ld, int col0, const WinGeom& g,
+                                           const Block& k, int vol, int NP, char* rows) {
+    const int tid = threadIdx.x;
+    constexpr int NCH = NPMAX * 4 / NT;
+    uint4 v[NCH];
+#pragma unroll
+    for (int j = 0; j < NCH; ++j) {
+        const int c = tid + NT * j, n = c >> 2, ch = c & 3;
+        v[j] = make_uint4(0, 0, 0, 0);
+        if (n < vol) {
+            const int64_t row = win_token_row(g, k.b, k.wi_t, k.wi_h, k.wi_w, n, nullptr);
+            v[j] = *reinterpret_cast<const uint4*>(src + row * ld + col0 + k.head * 32 + ch * 8);
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < NCH; ++j) {
+        const int c = tid + NT * j, n = c >> 2, ch = c & 3;
+        if (n < NP) *reinterpret_cast<uint4*>(rows + n * 64 + kchunk_swz(n, ch) * 16) = v[j];
+    }
+}
+
+__global__ void __launch_bounds__(NT)
+window_grad_rollout_cols_kernel(const uint16_t* __restrict__ qkv, int64_t ld, const uint16_t* __restrict__ dout,
+                                int64_t lddo, WinGeom g, FullWin fw, int heads, int vol, int NP,
+                                const float* __restrict__ table, int ntab, const float* __restrict__ mbuf,
+                                const float* __restrict__ wbuf, int64_t ntok, float* __restrict__ work) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    char* Qs = smem;
+    char* Ds = smem + (int64_t)NP * 64;
+    float* tab = reinterpret_cast<float*>(smem + (int64_t)NP * 128);
+    int* cl = reinterpret_cast<int*>(tab + (ntab + 3) / 4 * 4);
+    float* mrow = reinterpret_cast<float*>(cl + NP);
+    float* wrow = mrow + NP;
+    const Block k = decode_block(g, heads, (NP + 32 * WAVES - 1) / (32 * WAVES));
+    const int C = heads * 32;
+    stage(qkv, ld, 0, g, fw, k, heads, vol, NP, table, ntab, Qs, tab, cl);
+    stage_rows(dout, lddo, 0, g, k, vol, NP, Ds);
+    {
+        constexpr int NR = (NPMAX + NT - 1) / NT;
+        float mv[NR], wv[NR];
+#pragma unroll
+        for (int j = 0; j < NR; ++j) {
+            const int n = threadIdx.x + NT * j;
+            mv[j] = 0.f;  // a padded slot: weight 0 (and its region matches no key's)
+            wv[j] = 0.f;
+            if (n < vol) {
+                const int64_t row = win_token_row(g, k.b, k.wi_t, k.wi_h, k.wi_w, n, nullptr);
+                mv[j] = mbuf[(int64_t)k.head * ntok + row];
+                wv[j] = wbuf[(int64_t)k.head * ntok + row];
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < NR; ++j) {
+            const int n = threadIdx.x + NT * j;
+            if (n < NP) {
+                mrow[n] = mv[j];
+                wrow[n] = wv[j];
+            }
+        }
+    }
+    __syncthreads();  // the only barrier: a wave without keys leaves after it
+
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, rr = lane & 31, h = lane >> 5;
+    const int jb = k.spl * WAVES + wave;
+    if (jb * 32 >= vol) return;
+    const int kn = jb * 32 + rr;  // this lane's key (window-local)
+    const bool valid = kn < vol;
+    const int64_t krow = win_token_row(g, k.b, k.wi_t, k.wi_h, k.wi_w, valid ? kn : vol - 1, nullptr);
+    v8bf kf[2], vf[2];
+#pragma unroll
+    for (int kk = 0; kk < 2; ++kk) {
+        const uint16_t* p = qkv + krow * ld + k.head * 32 + 16 * kk + 8 * h;
+        kf[kk] = __builtin_bit_cast(v8bf, *reinterpret_cast<const v8s*>(p + C));
+        vf[kk] = __builtin_bit_cast(v8bf, *reinterpret_cast<const v8s*>(p + 2 * C));
+    }
+    const int clk = valid ? cl[kn] : LAB_NONE;
+    const int labk = clk & 15;
+    const int jk = rel_code_max(fw) - (clk >> 4);
+    int qoff[2];
+#pragma unroll
+    for (int kk = 0; kk < 2; ++kk) qoff[kk] = rr * 64 + kchunk_swz(rr, 2 * kk + h) * 16;
+
+    // S and dP blocks: reg 4g + e of lane (rr, h) = query 8g + 4h + e of the block, key rr; the queries in window order
+    float u = 0.f;
+    const int nqb = (vol + 31) / 32;
+    for (int ib = 0; ib < nqb; ++ib) {
+        v16f sc = v16f{}, dp = v16f{};
+#pragma unroll
+        for (int kk = 0; kk < 2; ++kk) {
+            const v8bf qf = __builtin_bit_cast(v8bf, *reinterpret_cast<const v8s*>(Qs + ib * 32 * 64 + qoff[kk]));
+            const v8bf df = __builtin_bit_cast(v8bf, *reinterpret_cast<const v8s*>(Ds + ib * 32 * 64 + qoff[kk]));
+            sc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qf, kf[kk], sc, 0, 0, 0);
+            dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(df, vf[kk], dp, 0, 0, 0);
+        }
+#pragma unroll
+        for (int g4 = 0; g4 < 4; ++g4) {
+            const int i0 = ib * 32 + 8 * g4 + 4 * h;
+            const int4 c4 = *reinterpret_cast<const int4*>(cl + i0);
+            const float4 m4 = *reinterpret_cast<const float4*>(mrow + i0);
+            const float4 w4 = *reinterpret_cast<const float4*>(wrow + i0);
+            const int cq[4] = {c4.x, c4.y, c4.z, c4.w};
+            const float mi[4] = {m4.x, m4.y, m4.z, m4.w}, wi[4] = {w4.x, w4.y, w4.z, w4.w};
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                // an excluded pair (another region, a padded slot, a lane without a key) adds an exact 0 whatever its dP
+                const bool on = (cq[e] & 15) == labk;
+                const float s = on ? sc[4 * g4 + e] + tab[(cq[e] >> 4) + jk] : -INFINITY;
+                const float d = on ? fmaxf(dp[4 * g4 + e], 0.f) : 0.f;
+                u = __builtin_fmaf(wi[e] * __builtin_amdgcn_exp2f(s - mi[e]), d, u);
+            }
+        }
+    }
+    u += __shfl_xor(u, 32, 64);  // the pair's two halves of the queries (a + b == b + a: the same bits in both lanes)
+    if (h == 0 && valid) work[(int64_t)k.head * ntok + krow] = u;
+}
+
+__global__ void __launch_bounds__(256) window_grad_rollout_finish(const float* __restrict__ work, const float* __restrict__ ain,
+                                                                 const float* __restrict__ base, int64_t ntok, int heads,
+                                                                 float alpha, float beta, float* __restrict__ aout,
+                                                                 float* __restrict__ rout) {
+    const int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (n >= ntok) return;
+    float a = 0.f;
+    for (int h = 0; h < heads; ++h) a += work[(int64_t)h * ntok + n];  // heads in head order
+    const float o = alpha * (a / (float)heads) + beta * ain[n];
+    aout[n] = o;
+    if (rout) rout[n] = o + base[n];
+}
+
 }  // namespace wroll
 }  // namespace vc
 
@@ -358,6 +504,78 @@ extern "C" int vc_window_rollout_step(const uint16_t* qkv, int64_t ld, const flo
     if (rc) return rc;
     window_rollout_finish<<<(unsigned)((ntok + 255) / 256), 256, 0, stream>>>(work, r_in, ntok, (int)heads, alpha, r_out);
     return check_launch("vc_window_rollout_step");
+}
+
+extern "C" int vc_window_grad_rollout_step(const uint16_t* qkv, int64_t ld, const uint16_t* dout, int64_t lddo,
+                                           const float* table, const float* r_in, const float* a_in, const float* base,
+                                           int64_t B, int64_t T, int64_t H, int64_t W, int64_t heads, int64_t head_dim,
+                                           int wt, int wh, int ww, int st, int sh, int sw, int full_t, int full_h,
+                                           int full_w, float alpha, float beta, float* work, int64_t work_elems,
+                                           float* a_out, float* r_out, hipStream_t stream) {
+    const char* me = "vc_window_grad_rollout_step";
+    auto bad = [&](int code, const char* what) { return fail(code, std::string(me) + ": " + what); };
+    if (!qkv || !dout || !table || !r_in || !a_in || !work || !a_out) return bad(VC_ERR_INVALID_ARG, "null pointer");
+    if (!base != !r_out) return bad(VC_ERR_INVALID_ARG, "base and r_out come together (both null or both given)");
+    if (head_dim != 32) return bad(VC_ERR_UNSUPPORTED, "head_dim must be 32");
+    if (B <= 0 || T <= 0 || H <= 0 || W <= 0 || heads <= 0 || T >= (1 << 20) || H >= (1 << 20) || W >= (1 << 20) ||
+        heads > 65535 || ld < 3 * heads * 32 || ld % 8 || lddo < heads * 32 || lddo % 8)
+        return bad(VC_ERR_INVALID_ARG, "bad shape / leading dimension");
+    if (wt <= 0 || wh <= 0 || ww <= 0 || T % wt || H % wh || W % ww)
+        return bad(VC_ERR_UNSUPPORTED, "the token grid must be whole windows (no padding)");
+    if (st < 0 || sh < 0 || sw < 0 || st >= wt || sh >= wh || sw >= ww)
+        return bad(VC_ERR_INVALID_ARG, "shift must be in [0, window)");
+    if (wt > full_t || wh > full_h || ww > full_w) return bad(VC_ERR_INVALID_ARG, "window larger than the full window");
+    if ((int64_t)full_t * full_h * full_w > NPMAX) return bad(VC_ERR_UNSUPPORTED, "full window volume > 448");
+    if ((((uintptr_t)qkv) | ((uintptr_t)dout)) & 15) return bad(VC_ERR_INVALID_ARG, "qkv and dout must be 16-byte aligned");
+    if ((((uintptr_t)table) | ((uintptr_t)r_in) | ((uintptr_t)a_in) | ((uintptr_t)base) | ((uintptr_t)work) |
+         ((uintptr_t)a_out) | ((uintptr_t)r_out)) & 3)
+        return bad(VC_ERR_INVALID_ARG, "f32 pointers must be 4-byte aligned");
+    const int vol = wt * wh * ww;
+    const int NP = (vol + 63) / 64 * 64;
+    const int64_t ntab = (int64_t)(2 * full_t - 1) * (2 * full_h - 1) * (2 * full_w - 1);
+    const int64_t lds = lds_bytes(NP, ntab), glds = grad_lds_bytes(NP, ntab);
+    // a guard for a larger NPMAX only: at a full-window volume <= 448 the table has < 3584 entries and glds stays
+    // under 78 KB, so today the volume check above is the one that refuses an oversized window
+    if (lds > LDS_MAX || glds > GLDS_MAX)
+        return bad(VC_ERR_UNSUPPORTED, "the window's q' and dO rows and the table column exceed the LDS");
+    if (T * H * W >= (1LL << 31) / B) return bad(VC_ERR_INVALID_ARG, "grid too large");
+    const int64_t ntok = B * T * H * W;
+    const int64_t nblk = ntok / vol * heads * ((NP + 32 * WAVES - 1) / (32 * WAVES));  // (window, head, 128 rows)
+    if (nblk > 0x7fffffff) return bad(VC_ERR_INVALID_ARG, "grid too large");
+    if (work_elems < 3 * heads * ntok) return bad(VC_ERR_INVALID_ARG, "work too small (3 * heads * B*T*H*W floats)");
+    const float* ins[3] = {r_in, a_in, base};
+    float* outs[2] = {a_out, r_out};
+    for (float* o : outs) {
+        if (!o) continue;
+        for (const float* i : ins)
+            if (i && overlap(o, ntok, i, ntok)) return bad(VC_ERR_INVALID_ARG, "a_out / r_out must not alias r_in, a_in or base");
+        if (overlap(work, work_elems, o, ntok)) return bad(VC_ERR_INVALID_ARG, "work must not alias an input or an output");
+    }
+    for (const float* i : ins)
+        if (i && overlap(work, work_elems, i, ntok)) return bad(VC_ERR_INVALID_ARG, "work must not alias an input or an output");
+    if (r_out && overlap(a_out, ntok, r_out, ntok)) return bad(VC_ERR_INVALID_ARG, "a_out must not alias r_out");
+    static bool attr_set = false;  // benign race (idempotent)
+    if (glds > 64 * 1024 && !attr_set) {
+        hipError_t e = hipFuncSetAttribute((const void*)window_grad_rollout_cols_kernel,
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)GLDS_MAX);
+        if (e != hipSuccess) return fail((int)e, std::string(me) + ": hipFuncSetAttribute: " + hipGetErrorString(e));
+        attr_set = true;
+    }
+    const WinGeom g{(int)T, (int)H, (int)W, wt, wh, ww, st, sh, sw, (int)(T / wt), (int)(H / wh), (int)(W / ww)};
+    const FullWin fw{full_t, full_h, full_w};
+    float* mbuf = work + heads * ntok;
+    float* wbuf = work + 2 * heads * ntok;
+    window_rollout_norm_kernel<<<(unsigned)nblk, NT, (size_t)lds, stream>>>(qkv, ld, g, fw, (int)heads, vol, NP, table,
+                                                                           (int)ntab, r_in, ntok, mbuf, wbuf);
+    int rc = check_launch(me);
+    if (rc) return rc;
+    window_grad_rollout_cols_kernel<<<(unsigned)nblk, NT, (size_t)glds, stream>>>(
+        qkv, ld, dout, lddo, g, fw, (int)heads, vol, NP, table, (int)ntab, mbuf, wbuf, ntok, work);
+    rc = check_launch(me);
+    if (rc) return rc;
+    window_grad_rollout_finish<<<(unsigned)((ntok + 255) / 256), 256, 0, stream>>>(work, a_in, base, ntok, (int)heads,
+                                                                                  alpha, beta, a_out, r_out);
+    return check_launch(me);
 }
 
 extern "C" int vc_merge_rollout_spread(const float* r_parent, int64_t B, int64_t T, int64_t H, int64_t W, float* r_child,

@@ -1050,6 +1050,50 @@ def window_rollout_step(qkv: torch.Tensor, table: torch.Tensor, r_in: torch.Tens
     return r_out
 
 
+def window_grad_rollout_work(B: int, grid, heads: int, device) -> torch.Tensor:
+    """the f32 scratch of window_grad_rollout_step: window_rollout_work's (three floats per (head, clip, token))"""
+    return window_rollout_work(B, grid, heads, device)
+
+
+def window_grad_rollout_step(qkv: torch.Tensor, dout: torch.Tensor, table: torch.Tensor, r_in: torch.Tensor,
+                             a_in: torch.Tensor, B: int, grid, heads: int, window, shift, full_window, alpha: float,
+                             beta: float, work: torch.Tensor, a_out: torch.Tensor, base: torch.Tensor | None = None,
+                             r_out: torch.Tensor | None = None) -> torch.Tensor:
+    """One block step of the gradient-weighted rollout through Swin's shifted-window attention
+    (vc_window_grad_rollout_step): a_out[j] = alpha * mean_h sum_{i in win(j)} r_in[i] P_h[i][j] max(dP_h[i][j], 0) +
+    beta * a_in[j] with dP_h[i][j] = dO_h[i] . v_j, and, when base and r_out are given (both or neither), r_out = a_out +
+    base.  qkv / table / window / shift / full_window as window_rollout_step takes them (v is read here); dout bf16
+    [>= B*T*H*W, >= heads*32] rows of dL/dO with any leading dimension that is a multiple of 8.  r_in / a_in / base /
+    a_out / r_out f32 [B*T*H*W]; the outputs alias no input; work from window_grad_rollout_work."""
+    _dev(qkv, dout, table, r_in, a_in, work, a_out)
+    T, H, W = grid
+    wt, wh, ww = window
+    st, sh, sw = shift
+    ft, fh, fw = full_window
+    ntok = B * T * H * W
+    ntab = (2 * ft - 1) * (2 * fh - 1) * (2 * fw - 1)
+    nm_ = "window_grad_rollout_step"
+    _need(qkv.dtype == torch.bfloat16 and qkv.dim() == 2 and qkv.stride(1) == 1, f"{nm_}: qkv bf16 rows")
+    _need(qkv.shape[1] >= 3 * heads * 32 and qkv.shape[0] >= ntok, f"{nm_}: qkv rows / columns")
+    _need(dout.dtype == torch.bfloat16 and dout.dim() == 2 and dout.stride(1) == 1, f"{nm_}: dout bf16 rows")
+    _need(dout.shape[1] >= heads * 32 and dout.shape[0] >= ntok, f"{nm_}: dout rows / columns")
+    _need(table.dtype == torch.float32 and table.is_contiguous() and tuple(table.shape) == (ntab, heads),
+          f"{nm_} table: f32 [ntab, heads]")
+    _need((base is None) == (r_out is None), f"{nm_}: base and r_out come together")
+    for t, nm in ((r_in, "r_in"), (a_in, "a_in"), (a_out, "a_out"), (base, "base"), (r_out, "r_out")):
+        if t is None:
+            continue
+        _dev(qkv, t)
+        _need(t.dtype == torch.float32 and t.is_contiguous() and t.numel() == ntok, f"{nm_}: {nm} f32 [B*T*H*W]")
+    _need(T % wt == 0 and H % wh == 0 and W % ww == 0, f"{nm_}: grid must be whole windows")
+    _need(work.dtype == torch.float32 and work.is_contiguous() and work.numel() >= 3 * heads * ntok,
+          f"{nm_} work: contiguous f32 [3*heads*B*T*H*W]")
+    _lib.call("vc_window_grad_rollout_step", _p(qkv), qkv.stride(0), _p(dout), dout.stride(0), _p(table), _p(r_in), _p(a_in),
+              None if base is None else _p(base), B, T, H, W, heads, 32, wt, wh, ww, st, sh, sw, ft, fh, fw, float(alpha),
+              float(beta), _p(work), work.numel(), _p(a_out), None if r_out is None else _p(r_out), _stream(qkv))
+    return a_out
+
+
 def merge_rollout_spread(r_parent: torch.Tensor, B: int, grid, r_child: torch.Tensor) -> torch.Tensor:
     """The rollout's hop through PatchMerging (vc_merge_rollout_spread): r_parent f32 [B*T*ceil(H/2)*ceil(W/2)] ->
     r_child f32 [B*T*H*W] on the child `grid` (T, H, W), every merged token's relevance shared equally among its

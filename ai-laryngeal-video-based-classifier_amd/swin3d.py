@@ -169,6 +169,11 @@ class Swin3d(FusedVideoModel):
         self._bias_cache = {}
         # kernel_events: a list collects HIP events around each window-attention launch (bench.py)
         self.stochastic_depth = True  # train step: torchvision's StochasticDepth on the residual branches
+        self._explain_class_ws = {}  # explain_class's buffers, apart from explain's (_explain_ws: 165 MB an entry)
+
+    def _drop_device_state(self):
+        super()._drop_device_state()
+        self._explain_class_ws = {}
 
     def _clean_state_dict(self, sd):  # relative_position_index: buffers, rebuilt
         return {k: v for k, v in super()._clean_state_dict(sd).items() if not k.endswith("relative_position_index")}
@@ -300,7 +305,7 @@ class Swin3d(FusedVideoModel):
         with torch.no_grad():
             return self.forward_logits(x).clone()  # the workspace buffer is reused by the next call
 
-    def _forward_train(self, video: torch.Tensor) -> torch.Tensor:
+    def _forward_train(self, video: torch.Tensor, *, frozen: bool = False, record: list | None = None) -> torch.Tensor:
         """torchvision's SwinTransformer3d forward (oracle/swin3d_ref.py) as autograd ops over the HIP
         kernels (vclip_amd/autograd_ops.py): bf16 MFMA GEMMs with fp32 accumulation on the fp32
         master weights, fp32 residual stream, exact GELU, the shifted-window attention with its
@@ -308,9 +313,16 @@ class Swin3d(FusedVideoModel):
         [B][T][H][W] rows throughout, PatchMerging's neighbour gather and the residual adds as torch
         layout glue.  Stochastic depth as torchvision's StochasticDepth(p_k, "row") on both residual
         branches of block k (p_k = stochastic_depth_prob * k / (blocks - 1); a per-clip keep mask
-        from torch's RNG, scaled by 1 / (1 - p_k)); `self.stochastic_depth = False` turns it off."""
+        from torch's RNG, scaled by 1 / (1 - p_k)); `self.stochastic_depth = False` turns it off.
+
+        The keyword arguments serve explain_class; their defaults leave the train step as it is.  `frozen`: the
+        masters enter detached (no backward forms a weight, bias or table gradient: autograd_ops skips them) and
+        stochastic depth is off.  `record`: a list that receives, per block in forward order, (q'|k|v as handed to
+        A.window_attention, its output o); the first block's o is made a leaf that requires grad, so a data-gradient
+        chain with respect to every block's o exists on frozen weights and ends there."""
         from . import autograd_ops as A
         c = self.cfg
+        P = (lambda n: self.P(n).detach()) if frozen else self.P  # noqa: E731
         B, Cin, T, H, W = video.shape
         if Cin != 3:
             raise ValueError("video must be [B, 3, T, H, W]")
@@ -323,12 +335,12 @@ class Swin3d(FusedVideoModel):
         K0 = 3 * pt * ph * pw
         a_emb = torch.zeros(_ru(M0, 256), _ru(K0, 64), dtype=torch.bfloat16, device=video.device)
         ops.tubelet_im2col(video, (pt, ph, pw), a_emb, layout="bcthw")
-        e = A.linear(a_emb[:M0, :K0], self.P("patch_embed.proj.weight").reshape(C0, K0), self.P("patch_embed.proj.bias"),
+        e = A.linear(a_emb[:M0, :K0], P("patch_embed.proj.weight").reshape(C0, K0), P("patch_embed.proj.bias"),
                      out_f32=True)
-        x = A.layer_norm(e, self.P("patch_embed.norm.weight"), self.P("patch_embed.norm.bias"), eps, out_bf16=False)
+        x = A.layer_norm(e, P("patch_embed.norm.weight"), P("patch_embed.norm.bias"), eps, out_bf16=False)
         full = tuple(c["window_size"])
         nblocks, k = sum(c["depths"]), 0
-        sd = c.get("stochastic_depth_prob", 0.0) if self.stochastic_depth else 0.0
+        sd = c.get("stochastic_depth_prob", 0.0) if self.stochastic_depth and not frozen else 0.0
 
         def drop_path(y, prob):  # torchvision StochasticDepth(prob, "row") on a [B * ntok, C] branch output
             if prob <= 0.0:
@@ -347,24 +359,28 @@ class Swin3d(FusedVideoModel):
                 window, shift = window_and_shift((t, h, w), full, shift_full)
                 pk_ = sd * k / (nblocks - 1) if nblocks > 1 else 0.0
                 k += 1
-                y = A.layer_norm(x, self.P(p + "norm1.weight"), self.P(p + "norm1.bias"), eps)
-                qkv = A.linear(y, self.P(p + "attn.qkv.weight"), self.P(p + "attn.qkv.bias"), qrows=C, qscale=qs)
-                o = A.window_attention(qkv, self.P(p + "attn.relative_position_bias_table"), B, (t, h, w), heads,
+                y = A.layer_norm(x, P(p + "norm1.weight"), P(p + "norm1.bias"), eps)
+                qkv = A.linear(y, P(p + "attn.qkv.weight"), P(p + "attn.qkv.bias"), qrows=C, qscale=qs)
+                o = A.window_attention(qkv, P(p + "attn.relative_position_bias_table"), B, (t, h, w), heads,
                                        window, shift, full)
-                x = x + drop_path(A.linear(o, self.P(p + "attn.proj.weight"), self.P(p + "attn.proj.bias"), out_f32=True),
+                if record is not None:
+                    if not o.requires_grad:
+                        o.requires_grad_()
+                    record.append((qkv, o))
+                x = x + drop_path(A.linear(o, P(p + "attn.proj.weight"), P(p + "attn.proj.bias"), out_f32=True),
                                   pk_)
-                y = A.layer_norm(x, self.P(p + "norm2.weight"), self.P(p + "norm2.bias"), eps)
-                hd = A.gelu_erf(A.linear(y, self.P(p + "mlp.0.weight"), self.P(p + "mlp.0.bias")))
-                x = x + drop_path(A.linear(hd, self.P(p + "mlp.3.weight"), self.P(p + "mlp.3.bias"), out_f32=True), pk_)
+                y = A.layer_norm(x, P(p + "norm2.weight"), P(p + "norm2.bias"), eps)
+                hd = A.gelu_erf(A.linear(y, P(p + "mlp.0.weight"), P(p + "mlp.0.bias")))
+                x = x + drop_path(A.linear(hd, P(p + "mlp.3.weight"), P(p + "mlp.3.bias"), out_f32=True), pk_)
             if s < len(c["depths"]) - 1:
                 p = f"features.{2 * s + 1}."
                 xv = x.reshape(B, t, h, w, C)
                 xv = torch.nn.functional.pad(xv, (0, 0, 0, w % 2, 0, h % 2))  # torchvision _patch_merging_pad
                 xm = torch.cat([xv[:, :, 0::2, 0::2], xv[:, :, 1::2, 0::2], xv[:, :, 0::2, 1::2], xv[:, :, 1::2, 1::2]], -1)
-                y = A.layer_norm(xm.reshape(-1, 4 * C), self.P(p + "norm.weight"), self.P(p + "norm.bias"), eps)
-                x = A.linear(y, self.P(p + "reduction.weight"), None, out_f32=True)
+                y = A.layer_norm(xm.reshape(-1, 4 * C), P(p + "norm.weight"), P(p + "norm.bias"), eps)
+                x = A.linear(y, P(p + "reduction.weight"), None, out_f32=True)
         t, h, w = grids[-1]
-        return A.pool_head(x, self.P("norm.weight"), self.P("norm.bias"), self.P("head.weight"), self.P("head.bias"), B,
+        return A.pool_head(x, P("norm.weight"), P("norm.bias"), P("head.weight"), P("head.bias"), B,
                            t * h * w, eps)
 
     # forward_logits (hosting.FusedVideoModel): under the stream split one part's small late-stage launches run
@@ -555,6 +571,134 @@ class Swin3d(FusedVideoModel):
         rd = rel.double()
         sal = (rd / rd.sum(dim=1, keepdim=True)).float().reshape(B, t0, h0, w0).contiguous()
         return Explanation(logits, rel, sal, sal.sum(dim=(2, 3)), method)
+
+    def _explain_class_buffers(self, B, grids, device):
+        """explain_class's rollout vectors per (B, geometry, device): per stage the two a and the two r buffers, the
+        step's scratch and `base`, the uniform seed carried through the hops alone (geometry only, made once)"""
+        key = (B, tuple(grids), str(device))
+        if key not in self._explain_class_ws:
+            if len(self._explain_class_ws) >= 2:
+                self._explain_class_ws = {}
+            c = self.cfg
+            f = lambda n: torch.zeros(n, dtype=torch.float32, device=device)  # noqa: E731
+            a, r, work, base = [], [], [], [None] * len(grids)
+            for s, (t, h, w) in enumerate(grids):
+                n = B * t * h * w
+                a.append((f(n), f(n)))
+                r.append((f(n), f(n)))
+                work.append(ops.window_grad_rollout_work(B, (t, h, w), c["num_heads"][s], device))
+            t, h, w = grids[-1]
+            base[-1] = torch.full((B * t * h * w,), 1.0 / (t * h * w), dtype=torch.float32).to(device)
+            for s in reversed(range(len(grids) - 1)):
+                t, h, w = grids[s]
+                base[s] = ops.merge_rollout_spread(base[s + 1], B, grids[s], f(B * t * h * w))
+            self._explain_class_ws[key] = dict(a=a, r=r, work=work, base=base)
+        return self._explain_class_ws[key]
+
+    def explain_class(self, video: torch.Tensor, target=None):
+        """The logits and which part of the clip speaks for ONE class: the gradient-weighted rollout of Chefer, Gur &
+        Wolf (2021) through the shifted-window attention of every block -- the class-specific sibling of
+        explain(method="rollout"), which is the same map whichever label is asked about.  Returns vivit.Explanation
+        with method "class_rollout": `logits` f32 [B, classes] on the device -- the TRAIN path's (the autograd chain
+        below; tests/test_swin3d_train_gpu.py bounds their distance to the inference logits at 5e-3 on its fixture);
+        on the host `token_relevance` f32 [B, N_0] >= 0 over stage 0's tokens (no CLS column), `saliency` f32
+        [B, T/pt, H/ph, W/pw] = token_relevance over its per-clip sum (all zero where that sum is exactly 0, as
+        ResNet3d's CAM) and `temporal` (saliency summed over space); `target` the B classes explained: None -> per clip
+        the argmax of the returned logits, an int -> that class for every clip, or B ints.
+
+        Per block, last first, with P_h the block's window probabilities and dP_h[i][j] = dO_h[i] . v_j the gradient
+        of the target logit with respect to them:  R <- R + mean_h(max(P_h dP_h, 0)) R.  The head reads the token
+        mean, so the carried row starts uniform over the last stage.  It is kept in two parts, r = base + a: base is
+        the seed carried through the PatchMerging hops alone (geometry only) and a the part that went through at least
+        one attention (per block a <- a + u(base + a), ops.window_grad_rollout_step; per hop
+        ops.merge_rollout_spread(a)).  The map is a at stage 0, never r - base: a is 1e-4 of base and a difference in
+        fp32 would be rounding noise.
+
+        The gradients come from the train step's autograd ops on DETACHED masters (_forward_train(frozen=True,
+        record=...), stochastic depth off) and torch.autograd.grad with respect to every block's attention output:
+        no weight-gradient GEMM, bias sum or table reduction runs (autograd_ops checks needs_input_grad), the patch
+        embedding's backward never runs and no parameter gets a .grad.  The forward's graphs, workspaces, bias cache
+        and packed weights are untouched.  Refuses (no fallback): training mode, CPU tensors, a video that is not
+        [B, 3, T, H, W] with T/H/W multiples of the patch size, stage grids that are not whole windows, a target
+        outside [0, classes) or not B of them."""
+        from .vivit import Explanation, VivitForVideoClassification
+        try:
+            target, scalar = VivitForVideoClassification._check_targets(target, self.num_classes)
+        except ValueError as e:  # the shared check names ViViT's method
+            raise ValueError(str(e).replace("explain:", "explain_class:", 1)) from None
+        if self.training:
+            raise RuntimeError("explain_class: inference only; call model.eval() first")
+        if video is None or video.device.type != "cuda":
+            raise RuntimeError("explain_class runs on the GPU only: move the clip batch to cuda")
+        if video.dim() != 5 or video.shape[1] != 3:
+            raise ValueError(f"video {tuple(video.shape)} must be [B, 3, T, H, W]")
+        B, _, T, H, W = video.shape
+        if target is not None:
+            target = target * B if scalar else target
+            if len(target) != B:
+                raise ValueError(f"explain_class: target has {len(target)} entries for {B} clips")
+        grids = self.geometry(B, T, H, W)  # ValueError unless T/H/W are multiples of the patch size
+        wins = self._block_windows(grids)
+        for s, g in enumerate(grids):
+            for window, _ in wins[s]:
+                if any(n % k for n, k in zip(g, window)):
+                    raise ValueError(f"explain_class: stage {s}'s token grid {g} is not whole windows of {tuple(window)}")
+        x = (video.contiguous().float() if video.dtype != torch.float32 else video.contiguous()).detach()
+        pk = self._pack(x.device)
+        buf = self._explain_class_buffers(B, grids, x.device)
+        logits, douts, kept = self._class_chain(x, target)
+        if target is None:
+            target = logits.argmax(dim=1).tolist()
+        with torch.no_grad():
+            a = self._class_rollout(buf, pk, kept, douts, B, grids, wins)
+            t0, h0, w0 = grids[0]
+            rel = a.cpu().reshape(B, t0 * h0 * w0)  # the one copy; the rest is host bookkeeping
+        rd = rel.double()
+        total = rd.sum(dim=1, keepdim=True)
+        sal = torch.where(total > 0, rd / torch.where(total > 0, total, torch.ones_like(total)), torch.zeros_like(rd))
+        sal = sal.float().reshape(B, t0, h0, w0).contiguous()
+        return Explanation(logits, rel, sal, sal.sum(dim=(2, 3)), "class_rollout", target=target)
+
+    def _class_chain(self, x, target, frozen: bool = True):
+        """explain_class's forward and data-gradient chain: (logits f32 [B, classes] detached, dL/dO of every block in
+        forward order for L = the sum of the target logits (target None: each clip's argmax), every block's kept
+        q'|k|v).  frozen=False runs the same chain, stochastic depth off as well, on the attached masters, so that
+        every backward forms its weight gradients (tools/saliency_time.py, and the test that the skips change no bit)."""
+        record = []
+        sd, self.stochastic_depth = self.stochastic_depth, False  # _forward_train turns it off itself only when frozen
+        try:
+            with torch.enable_grad():
+                out = self._forward_train(x, frozen=frozen, record=record)
+                idx = out.detach().argmax(dim=1) if target is None else torch.as_tensor(target, device=out.device)
+                sel = out.gather(1, idx.reshape(-1, 1)).sum()
+                douts = torch.autograd.grad(sel, [o for _, o in record])  # never .backward(): no parameter gets a .grad
+        finally:
+            self.stochastic_depth = sd
+        return out.detach(), douts, [q.detach() for q, _ in record]
+
+    def _class_rollout(self, buf, pk, kept, douts, B, grids, wins):
+        """the a / base rollout over the kept q'|k|v and dO of every block, last block first -> a at stage 0 (device)"""
+        c = self.cfg
+        full = tuple(c["window_size"])
+        first = [sum(c["depths"][:s]) for s in range(len(grids))]
+        last = len(grids) - 1
+        a_in, r_in = buf["a"][last][0].zero_(), buf["base"][last]
+        for s in reversed(range(len(grids))):
+            blocks = pk["stages"][s]["blocks"]
+            for i in reversed(range(len(blocks))):
+                window, shift = wins[s][i]
+                j = 1 if a_in is buf["a"][s][0] else 0
+                d = douts[first[s] + i]
+                if d.dtype != torch.bfloat16 or d.stride(1) != 1 or d.stride(0) % 8:
+                    d = d.to(torch.bfloat16).contiguous()
+                ops.window_grad_rollout_step(kept[first[s] + i], d, blocks[i]["table"], r_in, a_in, B, grids[s],
+                                             c["num_heads"][s], window, shift, full, 1.0, 1.0, buf["work"][s],
+                                             buf["a"][s][j], base=buf["base"][s], r_out=buf["r"][s][j])
+                a_in, r_in = buf["a"][s][j], buf["r"][s][j]
+            if s > 0:
+                a_in = ops.merge_rollout_spread(a_in, B, grids[s - 1], buf["a"][s - 1][0])
+                r_in = torch.add(a_in, buf["base"][s - 1], out=buf["r"][s - 1][0])
+        return a_in
 
 
 def create_model(logger=None, model_size="tiny", pretrained=True, num_classes=2, device="cuda", weights_seed: int = 0):

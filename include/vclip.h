@@ -643,6 +643,36 @@ int vc_window_rollout_step(const uint16_t* qkv, int64_t ld, const float* table, 
                            int64_t work_elems, float* r_out, hipStream_t stream);
 
 /*
+ * One block step of the class-specific, gradient-weighted rollout (Chefer, Gur & Wolf 2021) through Video
+ * Swin's shifted-window attention (csrc/window_rollout.hip).  qkv, table, the window / shift / full window
+ * and P_h exactly as vc_window_rollout_step takes and recomputes them; here v IS read (head h at column
+ * 2*heads*32 + 32h).  dout: dL/dO of this block's attention (before attn.proj), bf16 [>= B*T*H*W rows,
+ * >= heads*32], head h at columns 32h, leading dimension lddo -- the `dout` of vc_window_attention3d_bwd.
+ * dP_h[i][j] = dO_h[i] . v_j is the gradient of the target logit with respect to P_h[i][j] (bf16 MFMA,
+ * fp32 accumulation, the same operand arrangement as the scores).  With r_in the weights (base + a of the
+ * previous step) and a_in the carried attention part:
+ *     u[j]     = (1/heads) sum_h sum_{i in win(j)} r_in[i] * P_h[i][j] * max(dP_h[i][j], 0)
+ *     a_out[j] = alpha * u[j] + beta * a_in[j]
+ *     r_out[j] = a_out[j] + base[j]        (base and r_out: both NULL or both given)
+ * alpha = beta = 1 is one step of R <- R + mean_h(max(grad A . A, 0)) R with the identity path (base: the
+ * seed carried through the hops alone) kept apart from the part a that went through an attention; a is
+ * orders of magnitude below base, so it is never formed as a difference.  r_in, a_in, base, a_out, r_out
+ * f32 [B*T*H*W].  work: work_elems >= 3*heads*B*T*H*W floats, used as vc_window_rollout_step uses it.
+ * Three launches (the normaliser pass of vc_window_rollout_step, the column sums, the head sum in head
+ * order); no atomics: deterministic, and clip b's result does not depend on B.  No row of qkv or dout past
+ * B*T*H*W, no column past the ones named and no padded window slot reaches a result.  head_dim 32, whole
+ * windows, window volume <= 448; the window's q' and dO rows, the table column and the per-slot values
+ * must fit 160 KiB of LDS (72 KB at the 8x7x7 window), else VC_ERR_UNSUPPORTED before any launch.  a_out
+ * and r_out may alias neither r_in, a_in, base nor each other; work may alias none of them.
+ */
+int vc_window_grad_rollout_step(const uint16_t* qkv, int64_t ld, const uint16_t* dout, int64_t lddo,
+                                const float* table, const float* r_in, const float* a_in, const float* base,
+                                int64_t B, int64_t T, int64_t H, int64_t W, int64_t heads, int64_t head_dim, int wt,
+                                int wh, int ww, int st, int sh, int sw, int full_t, int full_h, int full_w,
+                                float alpha, float beta, float* work, int64_t work_elems, float* a_out,
+                                float* r_out, hipStream_t stream);
+
+/*
  * The rollout's hop through PatchMerging (csrc/window_rollout.hip): r_parent f32 [B*T*H2*W2] on the merged
  * grid (H2 = (H+1)/2, W2 = (W+1)/2) -> r_child f32 [B*T*H*W]; merged token (t, i, j) gives an equal share
  * of its relevance to each of its children (t, 2i + di, 2j + dj), di, dj in {0, 1}, that exist (a child

@@ -41,6 +41,16 @@ times Swin3d.explain: Swin-T, 32 x 224^2, B = 1, the same medians: forward_ms (t
 rollout_ms (the 12 ops.window_rollout_step calls and the 3 ops.merge_rollout_spread hops alone, on the q|k|v explain
 kept), forward_after_ms, and the size of the kept q|k|v.
 
+  python tools/saliency_time.py --family swin --class_rollout [--out profiles/swin_class_rollout_time.json]
+
+times Swin3d.explain_class instead, at the same size, the same medians: forward_ms, explain_rollout_ms (the class-blind
+map, for the ratio), explain_class_ms (the whole call: the train path's forward, the data-gradient chain, the 12
+gradient-weighted steps and 3 hops, the copy and the host part), chain_ms (the forward and the chain alone, frozen
+masters: no weight gradient formed), chain_with_weight_grads_ms (the same chain with every wgrad GEMM, bias sum and table
+reduction run), class_rollout_ms (the 12 ops.window_grad_rollout_step calls, the 3 hops and the 3 adds alone, on the
+q|k|v and dO of the last chain), plain_rollout_ms (the 12 ops.window_rollout_step calls and hops on the same q|k|v),
+class_rollout_extra_bytes (peak device memory of the first call above what was allocated before it) and forward_after_ms.
+
   python tools/saliency_time.py --family resnet3d [--out profiles/saliency_time_resnet3d.json]
 
 times ResNet3d.explain: ResNet3D-50, 32 x 224^2, B = 1, the same medians: forward_ms (the plain eager forward), then per
@@ -215,6 +225,97 @@ def swin(a) -> dict:
           f"{r['explain_rollout_ms']:.3f} ms, the rollout alone ({nsteps} steps + {len(grids) - 1} hops, "
           f"{r['rollout_launches']} launches) {r['rollout_ms']:.3f} ms ({r['rollout_tflops']:.1f} TFLOP/s); "
           f"kept q|k|v {r['kept_qkv_bytes'] / 1e6:.0f} MB", flush=True)
+    return {"model": "Swin-T 32 x 224^2", "reps": a.reps, "warmup": a.warmup, "build": source_hash(),
+            "device": torch.cuda.get_device_name(0), "batches": {str(B): r}}
+
+
+def swin_class(a) -> dict:
+    """Swin-T, 32 x 224^2, B = 1: Swin3d.explain_class whole, its forward + data-gradient chain alone with and without
+    the weight-gradient skips, and its 12 gradient-weighted steps alone beside the 12 plain steps on the same q|k|v"""
+    from vclip_amd import ops
+    from vclip_amd.build import source_hash
+    from vclip_amd.swin3d import create_model
+    from vclip_amd.weights import make_synthetic_video
+
+    model = create_model(None, "tiny", num_classes=2, device=DEV).eval()
+    c = model.cfg
+    B = 1
+    video = torch.from_numpy(make_synthetic_video(B, 32, 224, seed=1)).to(DEV)
+    grids = model.geometry(B, 32, 224, 224)
+    wins = model._block_windows(grids)
+    full = tuple(c["window_size"])
+
+    def forward():
+        model.forward_logits(video)
+
+    def explain():
+        model.explain(video, method="rollout")
+
+    def explain_class():
+        model.explain_class(video, target=0)
+
+    r = {"grids": [list(g) for g in grids], "forward_ms": _median(forward, a.reps, a.warmup),
+         "explain_rollout_ms": _median(explain, a.reps, a.warmup)}
+    model._explain_ws = {}  # explain's kept q|k|v must not count as already allocated
+    torch.cuda.synchronize()
+    base = torch.cuda.memory_allocated()
+    torch.cuda.reset_peak_memory_stats()
+    explain_class()
+    torch.cuda.synchronize()
+    r["class_rollout_extra_bytes"] = torch.cuda.max_memory_allocated() - base
+    r["explain_class_ms"] = _median(explain_class, a.reps, a.warmup)
+    kept = {}
+
+    def chain(frozen=True):
+        kept["logits"], kept["douts"], kept["qkv"] = model._class_chain(video, [0] * B, frozen=frozen)
+
+    r["chain_ms"] = _median(chain, a.reps, a.warmup)
+    r["chain_with_weight_grads_ms"] = _median(lambda: chain(False), a.reps, a.warmup)
+    chain()
+    buf, pk = model._explain_class_buffers(B, grids, video.device), model._packed
+
+    def class_steps():
+        model._class_rollout(buf, pk, kept["qkv"], kept["douts"], B, grids, wins)
+
+    work = [ops.window_rollout_work(B, g, c["num_heads"][s], DEV) for s, g in enumerate(grids)]
+    first = [sum(c["depths"][:s]) for s in range(len(grids))]
+
+    def plain_steps():
+        r_in = buf["base"][-1]
+        for s in reversed(range(len(grids))):
+            blocks = pk["stages"][s]["blocks"]
+            for i in reversed(range(len(blocks))):
+                window, shift = wins[s][i]
+                r_out = buf["r"][s][1] if r_in is buf["r"][s][0] else buf["r"][s][0]
+                ops.window_rollout_step(kept["qkv"][first[s] + i], blocks[i]["table"], r_in, B, grids[s], c["num_heads"][s],
+                                        window, shift, full, 0.5, work[s], r_out)
+                r_in = r_out
+            if s > 0:
+                r_in = ops.merge_rollout_spread(r_in, B, grids[s - 1], buf["r"][s - 1][0])
+
+    r["class_rollout_ms"] = _median(class_steps, a.reps, a.warmup)
+    r["plain_rollout_ms"] = _median(plain_steps, a.reps, a.warmup)
+    r["forward_after_ms"] = _median(forward, a.reps, a.warmup)
+    nsteps = sum(c["depths"])
+    r["class_rollout_launches"] = 3 * nsteps + 2 * (len(grids) - 1)
+    # per block 2 * 32 flop per (token, key of its window, head) and product: the normaliser's scores, then the column
+    # kernel's scores and dP
+    flop = 0.0
+    for s, (t, h, w) in enumerate(grids):
+        for window, _ in wins[s]:
+            flop += 3 * 2.0 * 32 * B * t * h * w * window[0] * window[1] * window[2] * c["num_heads"][s]
+    r["class_rollout_flop"] = flop
+    r["class_rollout_tflops"] = flop / (r["class_rollout_ms"] * 1e-3) / 1e12
+    r["grad_step_over_plain_step"] = r["class_rollout_ms"] / r["plain_rollout_ms"]
+    r["chain_skip_gain"] = r["chain_with_weight_grads_ms"] / r["chain_ms"]
+    r["explain_class_over_forward"] = r["explain_class_ms"] / r["forward_ms"]
+    r["explain_class_over_explain_rollout"] = r["explain_class_ms"] / r["explain_rollout_ms"]
+    print(f"Swin-T B = {B}: forward {r['forward_ms']:.3f} ms (after {r['forward_after_ms']:.3f}), explain(rollout) "
+          f"{r['explain_rollout_ms']:.3f} ms, explain_class {r['explain_class_ms']:.3f} ms; forward + data-gradient chain "
+          f"alone {r['chain_ms']:.3f} ms ({r['chain_with_weight_grads_ms']:.3f} ms with the weight gradients formed); the "
+          f"{nsteps} gradient-weighted steps + {len(grids) - 1} hops alone {r['class_rollout_ms']:.3f} ms "
+          f"({r['class_rollout_tflops']:.1f} TFLOP/s; the plain steps on the same q|k|v {r['plain_rollout_ms']:.3f} ms); peak "
+          f"extra memory {r['class_rollout_extra_bytes'] / 1e6:.0f} MB", flush=True)
     return {"model": "Swin-T 32 x 224^2", "reps": a.reps, "warmup": a.warmup, "build": source_hash(),
             "device": torch.cuda.get_device_name(0), "batches": {str(B): r}}
 
@@ -412,6 +513,7 @@ def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--family", choices=("vivit", "timesformer", "swin", "resnet3d", "lstm"), default="vivit")
     ap.add_argument("--check", action="store_true", help="time the perturbation test (vclip_amd.faithfulness) instead")
+    ap.add_argument("--class_rollout", action="store_true", help="with --family swin: time Swin3d.explain_class instead")
     ap.add_argument("--out", default=None)
     ap.add_argument("--reps", type=int, default=15)
     ap.add_argument("--warmup", type=int, default=3)
@@ -419,11 +521,15 @@ def main() -> int:
     if a.out is None:
         a.out = os.path.join(ROOT, "profiles", f"saliency_check_{a.family}.json" if a.check else
                              "saliency_time.json" if a.family == "vivit" else f"saliency_time_{a.family}.json")
+    if a.class_rollout and (a.family != "swin" or a.check):
+        ap.error("--class_rollout goes with --family swin, without --check")
+    if a.class_rollout and a.out == os.path.join(ROOT, "profiles", "saliency_time_swin.json"):
+        a.out = os.path.join(ROOT, "profiles", "swin_class_rollout_time.json")
     if not torch.cuda.is_available():
         raise SystemExit("saliency_time.py needs a GPU")
     if a.check or a.family in ("timesformer", "swin", "resnet3d", "lstm"):
         legs = {"timesformer": timesformer, "swin": swin, "resnet3d": resnet3d, "lstm": lstm}
-        res = check(a) if a.check else legs[a.family](a)
+        res = check(a) if a.check else swin_class(a) if a.class_rollout else legs[a.family](a)
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:
             json.dump(res, f, indent=1)
