@@ -192,9 +192,10 @@ rollout_partial_kernel(const uint16_t* __restrict__ qkv, int64_t ld, const uint1
     if (h == 0 && key < S) work[(int64_t)bh * S + key] = acc + other;
 }
 
-// r_out[b][j] = alpha * (1/H) sum_h work[b][h][j] + (1 - alpha) * r_in[b][j], heads in order
+// r_out[b][j] = alpha * (1/H) sum_h work[b][h][j] + beta * r_in[b][j], heads in order.  The plain step passes
+// beta = 1 - alpha, formed on the host in fp32: the same subtraction, so its bits stay as they are.
 __global__ void __launch_bounds__(256) rollout_combine_kernel(const float* __restrict__ work, const float* __restrict__ rin,
-                                                             int64_t n, int S, int H, float alpha,
+                                                             int64_t n, int S, int H, float alpha, float beta,
                                                              float* __restrict__ rout) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
@@ -202,21 +203,35 @@ __global__ void __launch_bounds__(256) rollout_combine_kernel(const float* __res
     const float* p = work + b * H * S + j;
     float u = 0.f;
     for (int hh = 0; hh < H; ++hh) u += p[(int64_t)hh * S];
-    rout[i] = alpha * (u / (float)H) + (1.0f - alpha) * rin[i];
+    rout[i] = alpha * (u / (float)H) + beta * rin[i];
 }
 
-// the same with its own weight on r_in: r_out[b][j] = alpha * (1/H) sum_h work[b][h][j] + beta * r_in[b][j].
-// Kept apart from the kernel above, whose (1 - alpha) is formed on the device: that one's bits stay as they are.
-__global__ void __launch_bounds__(256) grad_rollout_combine_kernel(const float* __restrict__ work,
-                                                                  const float* __restrict__ rin, int64_t n, int S, int H,
-                                                                  float alpha, float beta, float* __restrict__ rout) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const int64_t b = i / S, j = i - b * S;
-    const float* p = work + b * H * S + j;
-    float u = 0.f;
-    for (int hh = 0; hh < H; ++hh) u += p[(int64_t)hh * S];
-    rout[i] = alpha * (u / (float)H) + beta * rin[i];
+// both entries: validation and the two launches; `me` names the entry in the messages, `grad`: dout / lddo are used
+static int rollout_step(const char* me, bool grad, const uint16_t* qkv, int64_t ld, const uint16_t* dout, int64_t lddo,
+                        const float* lse, const float* r_in, int64_t B, int64_t S, int64_t H, int64_t head_dim, float alpha,
+                        float beta, float* work, int64_t work_elems, float* r_out, hipStream_t stream) {
+    auto bad = [&](int code, const char* what) { return fail(code, std::string(me) + ": " + what); };
+    if (!qkv || (grad && !dout) || !lse || !r_in || !work || !r_out) return bad(VC_ERR_INVALID_ARG, "null pointer");
+    if (head_dim != 64) return bad(VC_ERR_UNSUPPORTED, "head_dim must be 64");
+    if (B <= 0 || S <= 0 || H <= 0 || ld < 3 * H * 64 || ld % 8)
+        return bad(VC_ERR_INVALID_ARG, "bad shape / leading dimension");
+    if (grad && (lddo < H * 64 || lddo % 8)) return bad(VC_ERR_INVALID_ARG, "bad dO leading dimension");
+    if ((((uintptr_t)qkv) | ((uintptr_t)dout)) & 15)
+        return bad(VC_ERR_INVALID_ARG, grad ? "qkv and dO must be 16-byte aligned" : "qkv must be 16-byte aligned");
+    if ((((uintptr_t)lse) | ((uintptr_t)r_in) | ((uintptr_t)work) | ((uintptr_t)r_out)) & 3)
+        return bad(VC_ERR_INVALID_ARG, "f32 pointers must be 4-byte aligned");
+    if (B * H > 65535 || S > (1 << 24)) return bad(VC_ERR_INVALID_ARG, "grid too large");
+    if (work_elems < B * H * S) return bad(VC_ERR_INVALID_ARG, "work buffer too small");
+    if (work == r_in || work == r_out) return bad(VC_ERR_INVALID_ARG, "work must not alias r_in / r_out");
+    const dim3 grid((unsigned)((S + 127) / 128), (unsigned)(B * H));
+    if (grad)
+        rollout_partial_kernel<true><<<grid, 256, 0, stream>>>(qkv, ld, dout, lddo, lse, r_in, (int)S, (int)H, work);
+    else
+        rollout_partial_kernel<false><<<grid, 256, 0, stream>>>(qkv, ld, nullptr, 0, lse, r_in, (int)S, (int)H, work);
+    const int64_t n = B * S;
+    rollout_combine_kernel<<<(unsigned)((n + 255) / 256), 256, 0, stream>>>(work, r_in, n, (int)S, (int)H, alpha, beta,
+                                                                            r_out);
+    return check_launch(me);
 }
 
 }  // namespace roll
@@ -228,50 +243,14 @@ using namespace vc::roll;
 extern "C" int vc_attention_rollout_step(const uint16_t* qkv, int64_t ld, const float* lse, const float* r_in, int64_t B,
                                          int64_t S, int64_t H, int64_t head_dim, float alpha, float* work,
                                          int64_t work_elems, float* r_out, hipStream_t stream) {
-    if (!qkv || !lse || !r_in || !work || !r_out)
-        return fail(VC_ERR_INVALID_ARG, "vc_attention_rollout_step: null pointer");
-    if (head_dim != 64) return fail(VC_ERR_UNSUPPORTED, "vc_attention_rollout_step: head_dim must be 64");
-    if (B <= 0 || S <= 0 || H <= 0 || ld < 3 * H * 64 || ld % 8)
-        return fail(VC_ERR_INVALID_ARG, "vc_attention_rollout_step: bad shape / leading dimension");
-    if (((uintptr_t)qkv) & 15) return fail(VC_ERR_INVALID_ARG, "vc_attention_rollout_step: qkv must be 16-byte aligned");
-    if ((((uintptr_t)lse) | ((uintptr_t)r_in) | ((uintptr_t)work) | ((uintptr_t)r_out)) & 3)
-        return fail(VC_ERR_INVALID_ARG, "vc_attention_rollout_step: f32 pointers must be 4-byte aligned");
-    if (B * H > 65535 || S > (1 << 24)) return fail(VC_ERR_INVALID_ARG, "vc_attention_rollout_step: grid too large");
-    if (work_elems < B * H * S) return fail(VC_ERR_INVALID_ARG, "vc_attention_rollout_step: work buffer too small");
-    if (work == r_in || work == r_out)
-        return fail(VC_ERR_INVALID_ARG, "vc_attention_rollout_step: work must not alias r_in / r_out");
-    const dim3 grid((unsigned)((S + 127) / 128), (unsigned)(B * H));
-    rollout_partial_kernel<false><<<grid, 256, 0, stream>>>(qkv, ld, nullptr, 0, lse, r_in, (int)S, (int)H, work);
-    const int64_t n = B * S;
-    rollout_combine_kernel<<<(unsigned)((n + 255) / 256), 256, 0, stream>>>(work, r_in, n, (int)S, (int)H, alpha, r_out);
-    return check_launch("vc_attention_rollout_step");
+    return rollout_step("vc_attention_rollout_step", false, qkv, ld, nullptr, 0, lse, r_in, B, S, H, head_dim, alpha,
+                        1.0f - alpha, work, work_elems, r_out, stream);
 }
 
 extern "C" int vc_attention_grad_rollout_step(const uint16_t* qkv, int64_t ld, const uint16_t* dout, int64_t lddo,
                                               const float* lse, const float* r_in, int64_t B, int64_t S, int64_t H,
                                               int64_t head_dim, float alpha, float beta, float* work,
                                               int64_t work_elems, float* r_out, hipStream_t stream) {
-    if (!qkv || !dout || !lse || !r_in || !work || !r_out)
-        return fail(VC_ERR_INVALID_ARG, "vc_attention_grad_rollout_step: null pointer");
-    if (head_dim != 64) return fail(VC_ERR_UNSUPPORTED, "vc_attention_grad_rollout_step: head_dim must be 64");
-    if (B <= 0 || S <= 0 || H <= 0 || ld < 3 * H * 64 || ld % 8)
-        return fail(VC_ERR_INVALID_ARG, "vc_attention_grad_rollout_step: bad shape / leading dimension");
-    if (lddo < H * 64 || lddo % 8)
-        return fail(VC_ERR_INVALID_ARG, "vc_attention_grad_rollout_step: bad dO leading dimension");
-    if ((((uintptr_t)qkv) | ((uintptr_t)dout)) & 15)
-        return fail(VC_ERR_INVALID_ARG, "vc_attention_grad_rollout_step: qkv and dO must be 16-byte aligned");
-    if ((((uintptr_t)lse) | ((uintptr_t)r_in) | ((uintptr_t)work) | ((uintptr_t)r_out)) & 3)
-        return fail(VC_ERR_INVALID_ARG, "vc_attention_grad_rollout_step: f32 pointers must be 4-byte aligned");
-    if (B * H > 65535 || S > (1 << 24))
-        return fail(VC_ERR_INVALID_ARG, "vc_attention_grad_rollout_step: grid too large");
-    if (work_elems < B * H * S)
-        return fail(VC_ERR_INVALID_ARG, "vc_attention_grad_rollout_step: work buffer too small");
-    if (work == r_in || work == r_out)
-        return fail(VC_ERR_INVALID_ARG, "vc_attention_grad_rollout_step: work must not alias r_in / r_out");
-    const dim3 grid((unsigned)((S + 127) / 128), (unsigned)(B * H));
-    rollout_partial_kernel<true><<<grid, 256, 0, stream>>>(qkv, ld, dout, lddo, lse, r_in, (int)S, (int)H, work);
-    const int64_t n = B * S;
-    grad_rollout_combine_kernel<<<(unsigned)((n + 255) / 256), 256, 0, stream>>>(work, r_in, n, (int)S, (int)H, alpha,
-                                                                                  beta, r_out);
-    return check_launch("vc_attention_grad_rollout_step");
+    return rollout_step("vc_attention_grad_rollout_step", true, qkv, ld, dout, lddo, lse, r_in, B, S, H, head_dim, alpha,
+                        beta, work, work_elems, r_out, stream);
 }

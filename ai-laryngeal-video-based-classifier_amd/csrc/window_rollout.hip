@@ -16,11 +16,11 @@
 //                           32-key blocks: S^T = K . Q'^T, + bias (a gather from the head's table column in LDS),
 //                           region mask, online maximum m_i and sum l_i per block of 32 keys.  Stores m_i and
 //                           w_i = r_in[i] / l_i per (head, token) in the work buffer.
-//   window_rollout_cols_kernel  the column sums.  One workgroup per (window, head, 128 keys), the window's q' rows,
-//                           m and w in LDS; a wave holds 32 keys and walks the 32-query blocks in window order:
+//   window_rollout_cols_kernel<GRAD>  the column sums.  One workgroup per (window, head, 128 keys), the window's q'
+//                           rows, m and w in LDS; a wave holds 32 keys and walks the 32-query blocks in window order:
 //                           S = Q' . K^T (the same products and the same accumulation as above, operands swapped),
 //                           u_h[j] = sum_i w_i * exp2(s_ij - m_i).  u_h goes to work[h][row(j)]: no atomics.
-//   window_rollout_finish       r_out[n] = a * (sum_h work[h][n]) / heads + (1 - a) * r_in[n], heads in head order.
+//   window_rollout_finish<GRAD> r_out[n] = a * (sum_h work[h][n]) / heads + (1 - a) * r_in[n], heads in head order.
 // Splitting the window's rows over workgroups matters more than the pipe: the late stages have few (window, head)
 // pairs (Swin-T stage 4: 48), and one workgroup per pair left the device idle (the first version,
 // fdot2 on the VALU with one workgroup per pair, took 1.7 x the forward).  No lse input: the entry stands alone on
@@ -35,9 +35,11 @@
 // probabilities weighted by the positive part of their gradient dP_h[i][j] = dO_h[i] . v_j,
 //     u[j] = (1/heads) sum_h sum_{i in win(j)} r_in[i] * P_h[i][j] * max(dP_h[i][j], 0),
 //     a_out[j] = alpha * u[j] + beta * a_in[j],   r_out[j] = a_out[j] + base[j].
-// The normaliser kernel is reused as it is; window_grad_rollout_cols_kernel is the column kernel with the window's dO
-// rows staged beside its q' rows and the lane's v row read beside its k row, so both 32x32 products land in the same
-// registers (72 KB of LDS at the full window: the kernel's dynamic-LDS limit is raised).
+// The normaliser kernel is the same one; the column and finish kernels are the <true> instantiations of their
+// templates (as attention_rollout.hip's rollout_partial_kernel<GRAD>).  In the column kernel, under `if constexpr
+// (GRAD)`, the window's dO rows are staged beside its q' rows and the lane's v row is read beside its k row, so both
+// 32x32 products land in the same registers (72 KB of LDS at the full window: that instantiation's dynamic-LDS limit
+// is raised).  Both entries share step_setup (validation and geometry) and step_launch.
 #include "window_common.hpp"
 
 namespace vc {
@@ -45,6 +47,7 @@ namespace wroll {
 
 constexpr int NPMAX = 448;  // max padded window volume (8*7*7 = 392 -> 448)
 constexpr int64_t LDS_MAX = 64 * 1024;
+constexpr int64_t GLDS_MAX = 160 * 1024;  // the CU's LDS; above 64 KiB the kernel's dynamic-LDS limit is raised
 constexpr float LOG2E = 1.4426950408889634f;
 constexpr int LAB_PAD = 15;   // a padded window slot: its region matches no real token's (real codes are <= 7)
 constexpr int LAB_NONE = 14;  // a lane without a row: matches nothing, a padded slot included
@@ -55,6 +58,8 @@ constexpr int WAVES = NT / 64;
 // the head's table column f32 [ntab -> multiple of 4], per window slot cl int [NP] (rel_code << 4 | region code), and
 // in the column kernel mrow f32 [NP], wrow f32 [NP]
 __host__ __device__ inline int64_t lds_bytes(int64_t NP, int64_t ntab) { return NP * 64 + (ntab + 3) / 4 * 16 + NP * 12; }
+// the gradient column kernel: the dO rows [NP][64 B] after the q' rows, then the same (72 864 B at the full window)
+__host__ __device__ inline int64_t grad_lds_bytes(int64_t NP, int64_t ntab) { return lds_bytes(NP, ntab) + NP * 64; }
 
 struct Block {
     int b, wi_t, wi_h, wi_w, head, spl;
@@ -77,32 +82,37 @@ __device__ __forceinline__ Block decode_block(const WinGeom& g, int heads, int n
     return k;
 }
 
-// stage the window's rows of this head (col0: the column of the part wanted, 0 for q', heads*32 for k; zeros in the
-// padded slots), the table column scaled by log2 e, and every slot's (code, region)
+// stage the window's rows of this head from a row-major bf16 matrix (col0: the column of the part wanted, 0 for q' and
+// dO, heads*32 for k; zeros in the padded slots), 16-B chunks swizzled
+__device__ __forceinline__ void stage_rows(const uint16_t* __restrict__ src, int64_t ld, int col0, const WinGeom& g,
+                                           const Block& k, int vol, int NP, char* rows) {
+    const int tid = threadIdx.x;
+    // every load issued before the first LDS write (a rolled loop waits out one gather latency per NT chunks,
+    // as window.hip found): <= 7 chunks of 16 B per thread at NP = 448
+    constexpr int NCH = NPMAX * 4 / NT;
+    uint4 v[NCH];
+#pragma unroll
+    for (int j = 0; j < NCH; ++j) {
+        const int c = tid + NT * j, n = c >> 2, ch = c & 3;
+        v[j] = make_uint4(0, 0, 0, 0);
+        if (n < vol) {
+            const int64_t row = win_token_row(g, k.b, k.wi_t, k.wi_h, k.wi_w, n, nullptr);
+            v[j] = *reinterpret_cast<const uint4*>(src + row * ld + col0 + k.head * 32 + ch * 8);
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < NCH; ++j) {
+        const int c = tid + NT * j, n = c >> 2, ch = c & 3;
+        if (n < NP) *reinterpret_cast<uint4*>(rows + n * 64 + kchunk_swz(n, ch) * 16) = v[j];
+    }
+}
+
+// stage_rows of qkv, the table column scaled by log2 e, and every slot's (code, region)
 __device__ __forceinline__ void stage(const uint16_t* __restrict__ qkv, int64_t ld, int col0, const WinGeom& g,
                                       const FullWin& fw, const Block& k, int heads, int vol, int NP,
                                       const float* __restrict__ table, int ntab, char* rows, float* tab, int* cl) {
     const int tid = threadIdx.x;
-    {
-        // every load issued before the first LDS write (a rolled loop waits out one gather latency per NT chunks,
-        // as window.hip found): <= 7 chunks of 16 B per thread at NP = 448
-        constexpr int NCH = NPMAX * 4 / NT;
-        uint4 v[NCH];
-#pragma unroll
-        for (int j = 0; j < NCH; ++j) {
-            const int c = tid + NT * j, n = c >> 2, ch = c & 3;
-            v[j] = make_uint4(0, 0, 0, 0);
-            if (n < vol) {
-                const int64_t row = win_token_row(g, k.b, k.wi_t, k.wi_h, k.wi_w, n, nullptr);
-                v[j] = *reinterpret_cast<const uint4*>(qkv + row * ld + col0 + k.head * 32 + ch * 8);
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < NCH; ++j) {
-            const int c = tid + NT * j, n = c >> 2, ch = c & 3;
-            if (n < NP) *reinterpret_cast<uint4*>(rows + n * 64 + kchunk_swz(n, ch) * 16) = v[j];
-        }
-    }
+    stage_rows(qkv, ld, col0, g, k, vol, NP, rows);
     for (int i0 = 0; i0 < ntab; i0 += NT * 8) {  // the same for the table column, eight loads in flight
         float t[8];
 #pragma unroll
@@ -124,6 +134,32 @@ __device__ __forceinline__ void stage(const uint16_t* __restrict__ qkv, int64_t 
             v = (rel_code(n, fw) << 4) | lb;
         }
         cl[n] = v;
+    }
+}
+
+// stage every slot's row maximum and weight of this head (the normaliser kernel's), all loads before the first write
+__device__ __forceinline__ void stage_mw(const float* __restrict__ mbuf, const float* __restrict__ wbuf, int64_t ntok,
+                                         const WinGeom& g, const Block& k, int vol, int NP, float* mrow, float* wrow) {
+    constexpr int NR = (NPMAX + NT - 1) / NT;
+    float mv[NR], wv[NR];
+#pragma unroll
+    for (int j = 0; j < NR; ++j) {
+        const int n = threadIdx.x + NT * j;
+        mv[j] = 0.f;  // a padded slot: weight 0 (and its region matches no key's)
+        wv[j] = 0.f;
+        if (n < vol) {
+            const int64_t row = win_token_row(g, k.b, k.wi_t, k.wi_h, k.wi_w, n, nullptr);
+            mv[j] = mbuf[(int64_t)k.head * ntok + row];
+            wv[j] = wbuf[(int64_t)k.head * ntok + row];
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < NR; ++j) {
+        const int n = threadIdx.x + NT * j;
+        if (n < NP) {
+            mrow[n] = mv[j];
+            wrow[n] = wv[j];
+        }
     }
 }
 
@@ -199,42 +235,26 @@ window_rollout_norm_kernel(const uint16_t* __restrict__ qkv, int64_t ld, WinGeom
     }
 }
 
+// GRAD (the gradient-weighted step): a dO image after the Q' image (LDS: Q' rows, dO rows, table, cl, mrow, wrow), the
+// lane's v row in registers beside its k row, and a second MFMA chain dP = dO . V^T in the registers of S
+template <bool GRAD>
 __global__ void __launch_bounds__(NT)
-window_rollout_cols_kernel(const uint16_t* __restrict__ qkv, int64_t ld, WinGeom g, FullWin fw, int heads, int vol, int NP,
+window_rollout_cols_kernel(const uint16_t* __restrict__ qkv, int64_t ld, [[maybe_unused]] const uint16_t* __restrict__ dout,
+                           [[maybe_unused]] int64_t lddo, WinGeom g, FullWin fw, int heads, int vol, int NP,
                            const float* __restrict__ table, int ntab, const float* __restrict__ mbuf,
                            const float* __restrict__ wbuf, int64_t ntok, float* __restrict__ work) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* Qs = smem;
-    float* tab = reinterpret_cast<float*>(smem + (int64_t)NP * 64);
+    [[maybe_unused]] char* Ds = smem + (int64_t)NP * 64;
+    float* tab = reinterpret_cast<float*>(smem + (int64_t)NP * (GRAD ? 128 : 64));
     int* cl = reinterpret_cast<int*>(tab + (ntab + 3) / 4 * 4);
     float* mrow = reinterpret_cast<float*>(cl + NP);
     float* wrow = mrow + NP;
     const Block k = decode_block(g, heads, (NP + 32 * WAVES - 1) / (32 * WAVES));
     const int C = heads * 32;
     stage(qkv, ld, 0, g, fw, k, heads, vol, NP, table, ntab, Qs, tab, cl);
-    {
-        constexpr int NR = (NPMAX + NT - 1) / NT;
-        float mv[NR], wv[NR];
-#pragma unroll
-        for (int j = 0; j < NR; ++j) {
-            const int n = threadIdx.x + NT * j;
-            mv[j] = 0.f;  // a padded slot: weight 0 (and its region matches no key's)
-            wv[j] = 0.f;
-            if (n < vol) {
-                const int64_t row = win_token_row(g, k.b, k.wi_t, k.wi_h, k.wi_w, n, nullptr);
-                mv[j] = mbuf[(int64_t)k.head * ntok + row];
-                wv[j] = wbuf[(int64_t)k.head * ntok + row];
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < NR; ++j) {
-            const int n = threadIdx.x + NT * j;
-            if (n < NP) {
-                mrow[n] = mv[j];
-                wrow[n] = wv[j];
-            }
-        }
-    }
+    if constexpr (GRAD) stage_rows(dout, lddo, 0, g, k, vol, NP, Ds);
+    stage_mw(mbuf, wbuf, ntok, g, k, vol, NP, mrow, wrow);
     __syncthreads();  // the only barrier: a wave without keys leaves after it
 
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, rr = lane & 31, h = lane >> 5;
@@ -244,9 +264,13 @@ window_rollout_cols_kernel(const uint16_t* __restrict__ qkv, int64_t ld, WinGeom
     const bool valid = kn < vol;
     const int64_t krow = win_token_row(g, k.b, k.wi_t, k.wi_h, k.wi_w, valid ? kn : vol - 1, nullptr);
     v8bf kf[2];
+    [[maybe_unused]] v8bf vf[2];
 #pragma unroll
-    for (int kk = 0; kk < 2; ++kk)
-        kf[kk] = __builtin_bit_cast(v8bf, *reinterpret_cast<const v8s*>(qkv + krow * ld + C + k.head * 32 + 16 * kk + 8 * h));
+    for (int kk = 0; kk < 2; ++kk) {
+        const uint16_t* p = qkv + krow * ld + k.head * 32 + 16 * kk + 8 * h;
+        kf[kk] = __builtin_bit_cast(v8bf, *reinterpret_cast<const v8s*>(p + C));
+        if constexpr (GRAD) vf[kk] = __builtin_bit_cast(v8bf, *reinterpret_cast<const v8s*>(p + 2 * C));
+    }
     const int clk = valid ? cl[kn] : LAB_NONE;
     const int labk = clk & 15;
     const int jk = rel_code_max(fw) - (clk >> 4);
@@ -254,15 +278,20 @@ window_rollout_cols_kernel(const uint16_t* __restrict__ qkv, int64_t ld, WinGeom
 #pragma unroll
     for (int kk = 0; kk < 2; ++kk) qoff[kk] = rr * 64 + kchunk_swz(rr, 2 * kk + h) * 16;
 
-    // S block: reg 4g + e of lane (rr, h) = query 8g + 4h + e of the block, key rr; the queries in window order
+    // S (and dP) block: reg 4g + e of lane (rr, h) = query 8g + 4h + e of the block, key rr; the queries in window order
     float u = 0.f;
     const int nqb = (vol + 31) / 32;
     for (int ib = 0; ib < nqb; ++ib) {
         v16f sc = v16f{};
+        [[maybe_unused]] v16f dp = v16f{};
 #pragma unroll
         for (int kk = 0; kk < 2; ++kk) {
             const v8bf qf = __builtin_bit_cast(v8bf, *reinterpret_cast<const v8s*>(Qs + ib * 32 * 64 + qoff[kk]));
             sc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qf, kf[kk], sc, 0, 0, 0);
+            if constexpr (GRAD) {
+                const v8bf df = __builtin_bit_cast(v8bf, *reinterpret_cast<const v8s*>(Ds + ib * 32 * 64 + qoff[kk]));
+                dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(df, vf[kk], dp, 0, 0, 0);
+            }
         }
 #pragma unroll
         for (int g4 = 0; g4 < 4; ++g4) {
@@ -274,8 +303,16 @@ window_rollout_cols_kernel(const uint16_t* __restrict__ qkv, int64_t ld, WinGeom
             const float mi[4] = {m4.x, m4.y, m4.z, m4.w}, wi[4] = {w4.x, w4.y, w4.z, w4.w};
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                const float s = (cq[e] & 15) == labk ? sc[4 * g4 + e] + tab[(cq[e] >> 4) + jk] : -INFINITY;
-                u = __builtin_fmaf(wi[e], __builtin_amdgcn_exp2f(s - mi[e]), u);
+                const bool on = (cq[e] & 15) == labk;
+                const float s = on ? sc[4 * g4 + e] + tab[(cq[e] >> 4) + jk] : -INFINITY;
+                if constexpr (GRAD) {
+                    // an excluded pair (another region, a padded slot, a lane without a key) adds an exact 0 whatever
+                    // its dP.  The two forms differ on purpose: each keeps the bits it always had.
+                    const float d = on ? fmaxf(dp[4 * g4 + e], 0.f) : 0.f;
+                    u = __builtin_fmaf(wi[e] * __builtin_amdgcn_exp2f(s - mi[e]), d, u);
+                } else {
+                    u = __builtin_fmaf(wi[e], __builtin_amdgcn_exp2f(s - mi[e]), u);
+                }
             }
         }
     }
@@ -283,14 +320,26 @@ window_rollout_cols_kernel(const uint16_t* __restrict__ qkv, int64_t ld, WinGeom
     if (h == 0 && valid) work[(int64_t)k.head * ntok + krow] = u;
 }
 
-__global__ void __launch_bounds__(256) window_rollout_finish(const float* __restrict__ work, const float* __restrict__ rin,
-                                                            int64_t ntok, int heads, float alpha,
-                                                            float* __restrict__ rout) {
+// a_out[n] = alpha * (sum_h work[h][n]) / heads + beta * a_in[n].  GRAD: beta is given and, with base and r_out (both or
+// neither), r_out = a_out + base.  The plain step forms 1 - alpha here and keeps an expression of its own: it compiles
+// to two products and a sum, the beta form to a product and an FMA, so one expression for both would change its bits.
+template <bool GRAD>
+__global__ void __launch_bounds__(256) window_rollout_finish(const float* __restrict__ work, const float* __restrict__ ain,
+                                                            [[maybe_unused]] const float* __restrict__ base, int64_t ntok,
+                                                            int heads, float alpha, [[maybe_unused]] float beta,
+                                                            float* __restrict__ aout,
+                                                            [[maybe_unused]] float* __restrict__ rout) {
     const int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (n >= ntok) return;
     float a = 0.f;
     for (int h = 0; h < heads; ++h) a += work[(int64_t)h * ntok + n];  // heads in head order
-    rout[n] = alpha * (a / (float)heads) + (1.0f - alpha) * rin[n];
+    if constexpr (GRAD) {
+        const float o = alpha * (a / (float)heads) + beta * ain[n];
+        aout[n] = o;
+        if (rout) rout[n] = o + base[n];
+    } else {
+        aout[n] = alpha * (a / (float)heads) + (1.0f - alpha) * ain[n];
+    }
 }
 
 // child (bt, h, w) of parent (bt, h / 2, w / 2): the parent's relevance over the number of its children that exist
@@ -311,142 +360,96 @@ static bool overlap(const float* a, int64_t na, const float* b, int64_t nb) {
     return a0 < b0 + (uintptr_t)nb * 4 && b0 < a0 + (uintptr_t)na * 4;
 }
 
-// ---- the gradient-weighted step (vc_window_grad_rollout_step) ------------------------------------------------------
-// The column kernel with a second product: beside the q' rows the window's dO rows are staged, and the lane's v row
-// is read beside its k row, so dP = dO . V^T lands in the registers S = Q' . K^T lands in.
-constexpr int64_t GLDS_MAX = 160 * 1024;  // the CU's LDS; above 64 KiB the kernel's dynamic-LDS limit is raised
+// what a step entry derives from its arguments
+struct Step {
+    int vol, NP, ntab;
+    int64_t lds, glds, ntok, nblk;
+    WinGeom g;
+    FullWin fw;
+};
 
-// LDS of the gradient column kernel: lds_bytes plus the dO rows [NP][64 B] (72 864 B at the full window)
-__host__ __device__ inline int64_t grad_lds_bytes(int64_t NP, int64_t ntab) { return lds_bytes(NP, ntab) + NP * 64; }
-
-// the window's rows of this head from a row-major bf16 matrix (zeros in the padded slots), stage's chunk swizzle
-__device__ __forceinline__ void stage_rows(const uint16_t* __restrict__ src, int64_t ld, int col0, const WinGeom& g,
-                                           const Block& k, int vol, int NP, char* rows) {
-    const int tid = threadIdx.x;
-    constexpr int NCH = NPMAX * 4 / NT;
-    uint4 v[NCH];
-#pragma unroll
-    for (int j = 0; j < NCH; ++j) {
-        const int c = tid + NT * j, n = c >> 2, ch = c & 3;
-        v[j] = make_uint4(0, 0, 0, 0);
-        if (n < vol) {
-            const int64_t row = win_token_row(g, k.b, k.wi_t, k.wi_h, k.wi_w, n, nullptr);
-            v[j] = *reinterpret_cast<const uint4*>(src + row * ld + col0 + k.head * 32 + ch * 8);
-        }
+// The validation and the geometry the two step entries share; `me` names the entry in the messages.  `need`: the f32
+// pointers that must be given; base / r_out: the gradient step's optional pair (null in the plain step, which lists
+// its r_out in `need`); dout / lddo are looked at when `grad`.  Aliasing is each entry's own.
+static int step_setup(const char* me, bool grad, const uint16_t* qkv, int64_t ld, const uint16_t* dout, int64_t lddo,
+                      std::initializer_list<const float*> need, const float* base, const float* r_out, int64_t B,
+                      int64_t T, int64_t H, int64_t W, int64_t heads, int64_t head_dim, int wt, int wh, int ww, int st,
+                      int sh, int sw, int full_t, int full_h, int full_w, int64_t work_elems, Step& s) {
+    auto bad = [&](int code, const char* what) { return fail(code, std::string(me) + ": " + what); };
+    bool null = !qkv || (grad && !dout);
+    uintptr_t f32 = (uintptr_t)base | (uintptr_t)r_out;
+    for (const float* p : need) {
+        null |= !p;
+        f32 |= (uintptr_t)p;
     }
-#pragma unroll
-    for (int j = 0; j < NCH; ++j) {
-        const int c = tid + NT * j, n = c >> 2, ch = c & 3;
-        if (n < NP) *reinterpret_cast<uint4*>(rows + n * 64 + kchunk_swz(n, ch) * 16) = v[j];
-    }
+    if (null) return bad(VC_ERR_INVALID_ARG, "null pointer");
+    if (!base != !r_out) return bad(VC_ERR_INVALID_ARG, "base and r_out come together (both null or both given)");
+    if (head_dim != 32) return bad(VC_ERR_UNSUPPORTED, "head_dim must be 32");
+    if (B <= 0 || T <= 0 || H <= 0 || W <= 0 || heads <= 0 || T >= (1 << 20) || H >= (1 << 20) || W >= (1 << 20) ||
+        heads > 65535 || ld < 3 * heads * 32 || ld % 8 || (grad && (lddo < heads * 32 || lddo % 8)))
+        return bad(VC_ERR_INVALID_ARG, "bad shape / leading dimension");
+    if (wt <= 0 || wh <= 0 || ww <= 0 || T % wt || H % wh || W % ww)
+        return bad(VC_ERR_UNSUPPORTED, "the token grid must be whole windows (no padding)");
+    if (st < 0 || sh < 0 || sw < 0 || st >= wt || sh >= wh || sw >= ww)
+        return bad(VC_ERR_INVALID_ARG, "shift must be in [0, window)");
+    if (wt > full_t || wh > full_h || ww > full_w) return bad(VC_ERR_INVALID_ARG, "window larger than the full window");
+    if ((int64_t)full_t * full_h * full_w > NPMAX) return bad(VC_ERR_UNSUPPORTED, "full window volume > 448");
+    if ((((uintptr_t)qkv) | ((uintptr_t)dout)) & 15)
+        return bad(VC_ERR_INVALID_ARG, grad ? "qkv and dout must be 16-byte aligned" : "qkv must be 16-byte aligned");
+    if (f32 & 3) return bad(VC_ERR_INVALID_ARG, "f32 pointers must be 4-byte aligned");
+    s.vol = wt * wh * ww;
+    s.NP = (s.vol + 63) / 64 * 64;
+    const int64_t ntab = (int64_t)(2 * full_t - 1) * (2 * full_h - 1) * (2 * full_w - 1);
+    s.ntab = (int)ntab;
+    s.lds = lds_bytes(s.NP, ntab);
+    s.glds = grad_lds_bytes(s.NP, ntab);
+    // the gradient step's second bound is a guard for a larger NPMAX only: at a full-window volume <= 448 the table has
+    // < 3584 entries and glds stays under 78 KB, so today the volume check above is the one that refuses an oversized window
+    if (s.lds > LDS_MAX || (grad && s.glds > GLDS_MAX))
+        return bad(VC_ERR_UNSUPPORTED, grad ? "the window's q' and dO rows and the table column exceed the LDS"
+                                            : "the window's rows and the table column exceed the LDS");
+    if (T * H * W >= (1LL << 31) / B) return bad(VC_ERR_INVALID_ARG, "grid too large");
+    s.ntok = B * T * H * W;
+    s.nblk = s.ntok / s.vol * heads * ((s.NP + 32 * WAVES - 1) / (32 * WAVES));  // (window, head, 128 rows)
+    if (s.nblk > 0x7fffffff) return bad(VC_ERR_INVALID_ARG, "grid too large");
+    if (work_elems < 3 * heads * s.ntok) return bad(VC_ERR_INVALID_ARG, "work too small (3 * heads * B*T*H*W floats)");
+    s.g = WinGeom{(int)T, (int)H, (int)W, wt, wh, ww, st, sh, sw, (int)(T / wt), (int)(H / wh), (int)(W / ww)};
+    s.fw = FullWin{full_t, full_h, full_w};
+    return 0;
 }
 
-__global__ void __launch_bounds__(NT)
-window_grad_rollout_cols_kernel(const uint16_t* __restrict__ qkv, int64_t ld, const uint16_t* __restrict__ dout,
-                                int64_t lddo, WinGeom g, FullWin fw, int heads, int vol, int NP,
-                                const float* __restrict__ table, int ntab, const float* __restrict__ mbuf,
-                                const float* __restrict__ wbuf, int64_t ntok, float* __restrict__ work) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    char* Qs = smem;
-    char* Ds = smem + (int64_t)NP * 64;
-    float* tab = reinterpret_cast<float*>(smem + (int64_t)NP * 128);
-    int* cl = reinterpret_cast<int*>(tab + (ntab + 3) / 4 * 4);
-    float* mrow = reinterpret_cast<float*>(cl + NP);
-    float* wrow = mrow + NP;
-    const Block k = decode_block(g, heads, (NP + 32 * WAVES - 1) / (32 * WAVES));
-    const int C = heads * 32;
-    stage(qkv, ld, 0, g, fw, k, heads, vol, NP, table, ntab, Qs, tab, cl);
-    stage_rows(dout, lddo, 0, g, k, vol, NP, Ds);
-    {
-        constexpr int NR = (NPMAX + NT - 1) / NT;
-        float mv[NR], wv[NR];
-#pragma unroll
-        for (int j = 0; j < NR; ++j) {
-            const int n = threadIdx.x + NT * j;
-            mv[j] = 0.f;  // a padded slot: weight 0 (and its region matches no key's)
-            wv[j] = 0.f;
-            if (n < vol) {
-                const int64_t row = win_token_row(g, k.b, k.wi_t, k.wi_h, k.wi_w, n, nullptr);
-                mv[j] = mbuf[(int64_t)k.head * ntok + row];
-                wv[j] = wbuf[(int64_t)k.head * ntok + row];
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < NR; ++j) {
-            const int n = threadIdx.x + NT * j;
-            if (n < NP) {
-                mrow[n] = mv[j];
-                wrow[n] = wv[j];
-            }
-        }
+// the three launches; dout given: the gradient-weighted column kernel
+static int step_launch(const char* me, const Step& s, const uint16_t* qkv, int64_t ld, const uint16_t* dout, int64_t lddo,
+                       const float* table, const float* r_in, const float* a_in, const float* base, int heads, float alpha,
+                       float beta, float* work, float* a_out, float* r_out, hipStream_t stream) {
+    static bool attr_set = false;  // benign race (idempotent)
+    if (dout && s.glds > 64 * 1024 && !attr_set) {
+        hipError_t e = hipFuncSetAttribute((const void*)window_rollout_cols_kernel<true>,
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)GLDS_MAX);
+        if (e != hipSuccess) return fail((int)e, std::string(me) + ": hipFuncSetAttribute: " + hipGetErrorString(e));
+        attr_set = true;
     }
-    __syncthreads();  // the only barrier: a wave without keys leaves after it
-
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, rr = lane & 31, h = lane >> 5;
-    const int jb = k.spl * WAVES + wave;
-    if (jb * 32 >= vol) return;
-    const int kn = jb * 32 + rr;  // this lane's key (window-local)
-    const bool valid = kn < vol;
-    const int64_t krow = win_token_row(g, k.b, k.wi_t, k.wi_h, k.wi_w, valid ? kn : vol - 1, nullptr);
-    v8bf kf[2], vf[2];
-#pragma unroll
-    for (int kk = 0; kk < 2; ++kk) {
-        const uint16_t* p = qkv + krow * ld + k.head * 32 + 16 * kk + 8 * h;
-        kf[kk] = __builtin_bit_cast(v8bf, *reinterpret_cast<const v8s*>(p + C));
-        vf[kk] = __builtin_bit_cast(v8bf, *reinterpret_cast<const v8s*>(p + 2 * C));
-    }
-    const int clk = valid ? cl[kn] : LAB_NONE;
-    const int labk = clk & 15;
-    const int jk = rel_code_max(fw) - (clk >> 4);
-    int qoff[2];
-#pragma unroll
-    for (int kk = 0; kk < 2; ++kk) qoff[kk] = rr * 64 + kchunk_swz(rr, 2 * kk + h) * 16;
-
-    // S and dP blocks: reg 4g + e of lane (rr, h) = query 8g + 4h + e of the block, key rr; the queries in window order
-    float u = 0.f;
-    const int nqb = (vol + 31) / 32;
-    for (int ib = 0; ib < nqb; ++ib) {
-        v16f sc = v16f{}, dp = v16f{};
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk) {
-            const v8bf qf = __builtin_bit_cast(v8bf, *reinterpret_cast<const v8s*>(Qs + ib * 32 * 64 + qoff[kk]));
-            const v8bf df = __builtin_bit_cast(v8bf, *reinterpret_cast<const v8s*>(Ds + ib * 32 * 64 + qoff[kk]));
-            sc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qf, kf[kk], sc, 0, 0, 0);
-            dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(df, vf[kk], dp, 0, 0, 0);
-        }
-#pragma unroll
-        for (int g4 = 0; g4 < 4; ++g4) {
-            const int i0 = ib * 32 + 8 * g4 + 4 * h;
-            const int4 c4 = *reinterpret_cast<const int4*>(cl + i0);
-            const float4 m4 = *reinterpret_cast<const float4*>(mrow + i0);
-            const float4 w4 = *reinterpret_cast<const float4*>(wrow + i0);
-            const int cq[4] = {c4.x, c4.y, c4.z, c4.w};
-            const float mi[4] = {m4.x, m4.y, m4.z, m4.w}, wi[4] = {w4.x, w4.y, w4.z, w4.w};
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                // an excluded pair (another region, a padded slot, a lane without a key) adds an exact 0 whatever its dP
-                const bool on = (cq[e] & 15) == labk;
-                const float s = on ? sc[4 * g4 + e] + tab[(cq[e] >> 4) + jk] : -INFINITY;
-                const float d = on ? fmaxf(dp[4 * g4 + e], 0.f) : 0.f;
-                u = __builtin_fmaf(wi[e] * __builtin_amdgcn_exp2f(s - mi[e]), d, u);
-            }
-        }
-    }
-    u += __shfl_xor(u, 32, 64);  // the pair's two halves of the queries (a + b == b + a: the same bits in both lanes)
-    if (h == 0 && valid) work[(int64_t)k.head * ntok + krow] = u;
-}
-
-__global__ void __launch_bounds__(256) window_grad_rollout_finish(const float* __restrict__ work, const float* __restrict__ ain,
-                                                                 const float* __restrict__ base, int64_t ntok, int heads,
-                                                                 float alpha, float beta, float* __restrict__ aout,
-                                                                 float* __restrict__ rout) {
-    const int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (n >= ntok) return;
-    float a = 0.f;
-    for (int h = 0; h < heads; ++h) a += work[(int64_t)h * ntok + n];  // heads in head order
-    const float o = alpha * (a / (float)heads) + beta * ain[n];
-    aout[n] = o;
-    if (rout) rout[n] = o + base[n];
+    const unsigned nblk = (unsigned)s.nblk;
+    float* mbuf = work + heads * s.ntok;
+    float* wbuf = work + 2 * heads * s.ntok;
+    window_rollout_norm_kernel<<<nblk, NT, (size_t)s.lds, stream>>>(qkv, ld, s.g, s.fw, heads, s.vol, s.NP, table, s.ntab,
+                                                                    r_in, s.ntok, mbuf, wbuf);
+    int rc = check_launch(me);
+    if (rc) return rc;
+    if (dout)
+        window_rollout_cols_kernel<true><<<nblk, NT, (size_t)s.glds, stream>>>(
+            qkv, ld, dout, lddo, s.g, s.fw, heads, s.vol, s.NP, table, s.ntab, mbuf, wbuf, s.ntok, work);
+    else
+        window_rollout_cols_kernel<false><<<nblk, NT, (size_t)s.lds, stream>>>(
+            qkv, ld, nullptr, 0, s.g, s.fw, heads, s.vol, s.NP, table, s.ntab, mbuf, wbuf, s.ntok, work);
+    rc = check_launch(me);
+    if (rc) return rc;
+    const unsigned nfin = (unsigned)((s.ntok + 255) / 256);
+    if (dout)
+        window_rollout_finish<true><<<nfin, 256, 0, stream>>>(work, a_in, base, s.ntok, heads, alpha, beta, a_out, r_out);
+    else
+        window_rollout_finish<false><<<nfin, 256, 0, stream>>>(work, a_in, nullptr, s.ntok, heads, alpha, 0.f, a_out, nullptr);
+    return check_launch(me);
 }
 
 }  // namespace wroll
@@ -459,51 +462,17 @@ extern "C" int vc_window_rollout_step(const uint16_t* qkv, int64_t ld, const flo
                                       int64_t T, int64_t H, int64_t W, int64_t heads, int64_t head_dim, int wt, int wh,
                                       int ww, int st, int sh, int sw, int full_t, int full_h, int full_w, float alpha,
                                       float* work, int64_t work_elems, float* r_out, hipStream_t stream) {
-    if (!qkv || !table || !r_in || !work || !r_out) return fail(VC_ERR_INVALID_ARG, "vc_window_rollout_step: null pointer");
-    if (head_dim != 32) return fail(VC_ERR_UNSUPPORTED, "vc_window_rollout_step: head_dim must be 32");
-    if (B <= 0 || T <= 0 || H <= 0 || W <= 0 || heads <= 0 || T >= (1 << 20) || H >= (1 << 20) || W >= (1 << 20) ||
-        heads > 65535 || ld < 3 * heads * 32 || ld % 8)
-        return fail(VC_ERR_INVALID_ARG, "vc_window_rollout_step: bad shape / leading dimension");
-    if (wt <= 0 || wh <= 0 || ww <= 0 || T % wt || H % wh || W % ww)
-        return fail(VC_ERR_UNSUPPORTED, "vc_window_rollout_step: the token grid must be whole windows (no padding)");
-    if (st < 0 || sh < 0 || sw < 0 || st >= wt || sh >= wh || sw >= ww)
-        return fail(VC_ERR_INVALID_ARG, "vc_window_rollout_step: shift must be in [0, window)");
-    if (wt > full_t || wh > full_h || ww > full_w)
-        return fail(VC_ERR_INVALID_ARG, "vc_window_rollout_step: window larger than the full window");
-    if ((int64_t)full_t * full_h * full_w > NPMAX)
-        return fail(VC_ERR_UNSUPPORTED, "vc_window_rollout_step: full window volume > 448");
-    if (((uintptr_t)qkv) & 15) return fail(VC_ERR_INVALID_ARG, "vc_window_rollout_step: qkv must be 16-byte aligned");
-    if ((((uintptr_t)table) | ((uintptr_t)r_in) | ((uintptr_t)work) | ((uintptr_t)r_out)) & 3)
-        return fail(VC_ERR_INVALID_ARG, "vc_window_rollout_step: f32 pointers must be 4-byte aligned");
-    const int vol = wt * wh * ww;
-    const int NP = (vol + 63) / 64 * 64;
-    const int64_t ntab = (int64_t)(2 * full_t - 1) * (2 * full_h - 1) * (2 * full_w - 1);
-    const int64_t lds = lds_bytes(NP, ntab);
-    if (lds > LDS_MAX)
-        return fail(VC_ERR_UNSUPPORTED, "vc_window_rollout_step: the window's rows and the table column exceed the LDS");
-    if (T * H * W >= (1LL << 31) / B) return fail(VC_ERR_INVALID_ARG, "vc_window_rollout_step: grid too large");
-    const int64_t ntok = B * T * H * W;
-    const int64_t nblk = ntok / vol * heads * ((NP + 32 * WAVES - 1) / (32 * WAVES));  // (window, head, 128 rows)
-    if (nblk > 0x7fffffff) return fail(VC_ERR_INVALID_ARG, "vc_window_rollout_step: grid too large");
-    if (work_elems < 3 * heads * ntok)
-        return fail(VC_ERR_INVALID_ARG, "vc_window_rollout_step: work too small (3 * heads * B*T*H*W floats)");
-    if (overlap(r_out, ntok, r_in, ntok)) return fail(VC_ERR_INVALID_ARG, "vc_window_rollout_step: r_out must not alias r_in");
-    if (overlap(work, work_elems, r_in, ntok) || overlap(work, work_elems, r_out, ntok))
-        return fail(VC_ERR_INVALID_ARG, "vc_window_rollout_step: work must not alias r_in or r_out");
-    const WinGeom g{(int)T, (int)H, (int)W, wt, wh, ww, st, sh, sw, (int)(T / wt), (int)(H / wh), (int)(W / ww)};
-    const FullWin fw{full_t, full_h, full_w};
-    float* mbuf = work + heads * ntok;
-    float* wbuf = work + 2 * heads * ntok;
-    window_rollout_norm_kernel<<<(unsigned)nblk, NT, (size_t)lds, stream>>>(qkv, ld, g, fw, (int)heads, vol, NP, table,
-                                                                           (int)ntab, r_in, ntok, mbuf, wbuf);
-    int rc = check_launch("vc_window_rollout_step");
-    if (rc) return rc;
-    window_rollout_cols_kernel<<<(unsigned)nblk, NT, (size_t)lds, stream>>>(qkv, ld, g, fw, (int)heads, vol, NP, table,
-                                                                           (int)ntab, mbuf, wbuf, ntok, work);
-    rc = check_launch("vc_window_rollout_step");
-    if (rc) return rc;
-    window_rollout_finish<<<(unsigned)((ntok + 255) / 256), 256, 0, stream>>>(work, r_in, ntok, (int)heads, alpha, r_out);
-    return check_launch("vc_window_rollout_step");
+    const char* me = "vc_window_rollout_step";
+    Step s;
+    if (int rc = step_setup(me, false, qkv, ld, nullptr, 0, {table, r_in, work, r_out}, nullptr, nullptr, B, T, H, W, heads,
+                            head_dim, wt, wh, ww, st, sh, sw, full_t, full_h, full_w, work_elems, s))
+        return rc;
+    if (overlap(r_out, s.ntok, r_in, s.ntok)) return fail(VC_ERR_INVALID_ARG, std::string(me) + ": r_out must not alias r_in");
+    if (overlap(work, work_elems, r_in, s.ntok) || overlap(work, work_elems, r_out, s.ntok))
+        return fail(VC_ERR_INVALID_ARG, std::string(me) + ": work must not alias r_in or r_out");
+    // the finish kernel with r_in / r_out for a_in / a_out
+    return step_launch(me, s, qkv, ld, nullptr, 0, table, r_in, r_in, nullptr, (int)heads, alpha, 0.f, work, r_out, nullptr,
+                       stream);
 }
 
 extern "C" int vc_window_grad_rollout_step(const uint16_t* qkv, int64_t ld, const uint16_t* dout, int64_t lddo,
@@ -513,69 +482,25 @@ extern "C" int vc_window_grad_rollout_step(const uint16_t* qkv, int64_t ld, cons
                                            int full_w, float alpha, float beta, float* work, int64_t work_elems,
                                            float* a_out, float* r_out, hipStream_t stream) {
     const char* me = "vc_window_grad_rollout_step";
-    auto bad = [&](int code, const char* what) { return fail(code, std::string(me) + ": " + what); };
-    if (!qkv || !dout || !table || !r_in || !a_in || !work || !a_out) return bad(VC_ERR_INVALID_ARG, "null pointer");
-    if (!base != !r_out) return bad(VC_ERR_INVALID_ARG, "base and r_out come together (both null or both given)");
-    if (head_dim != 32) return bad(VC_ERR_UNSUPPORTED, "head_dim must be 32");
-    if (B <= 0 || T <= 0 || H <= 0 || W <= 0 || heads <= 0 || T >= (1 << 20) || H >= (1 << 20) || W >= (1 << 20) ||
-        heads > 65535 || ld < 3 * heads * 32 || ld % 8 || lddo < heads * 32 || lddo % 8)
-        return bad(VC_ERR_INVALID_ARG, "bad shape / leading dimension");
-    if (wt <= 0 || wh <= 0 || ww <= 0 || T % wt || H % wh || W % ww)
-        return bad(VC_ERR_UNSUPPORTED, "the token grid must be whole windows (no padding)");
-    if (st < 0 || sh < 0 || sw < 0 || st >= wt || sh >= wh || sw >= ww)
-        return bad(VC_ERR_INVALID_ARG, "shift must be in [0, window)");
-    if (wt > full_t || wh > full_h || ww > full_w) return bad(VC_ERR_INVALID_ARG, "window larger than the full window");
-    if ((int64_t)full_t * full_h * full_w > NPMAX) return bad(VC_ERR_UNSUPPORTED, "full window volume > 448");
-    if ((((uintptr_t)qkv) | ((uintptr_t)dout)) & 15) return bad(VC_ERR_INVALID_ARG, "qkv and dout must be 16-byte aligned");
-    if ((((uintptr_t)table) | ((uintptr_t)r_in) | ((uintptr_t)a_in) | ((uintptr_t)base) | ((uintptr_t)work) |
-         ((uintptr_t)a_out) | ((uintptr_t)r_out)) & 3)
-        return bad(VC_ERR_INVALID_ARG, "f32 pointers must be 4-byte aligned");
-    const int vol = wt * wh * ww;
-    const int NP = (vol + 63) / 64 * 64;
-    const int64_t ntab = (int64_t)(2 * full_t - 1) * (2 * full_h - 1) * (2 * full_w - 1);
-    const int64_t lds = lds_bytes(NP, ntab), glds = grad_lds_bytes(NP, ntab);
-    // a guard for a larger NPMAX only: at a full-window volume <= 448 the table has < 3584 entries and glds stays
-    // under 78 KB, so today the volume check above is the one that refuses an oversized window
-    if (lds > LDS_MAX || glds > GLDS_MAX)
-        return bad(VC_ERR_UNSUPPORTED, "the window's q' and dO rows and the table column exceed the LDS");
-    if (T * H * W >= (1LL << 31) / B) return bad(VC_ERR_INVALID_ARG, "grid too large");
-    const int64_t ntok = B * T * H * W;
-    const int64_t nblk = ntok / vol * heads * ((NP + 32 * WAVES - 1) / (32 * WAVES));  // (window, head, 128 rows)
-    if (nblk > 0x7fffffff) return bad(VC_ERR_INVALID_ARG, "grid too large");
-    if (work_elems < 3 * heads * ntok) return bad(VC_ERR_INVALID_ARG, "work too small (3 * heads * B*T*H*W floats)");
+    auto bad = [&](const char* what) { return fail(VC_ERR_INVALID_ARG, std::string(me) + ": " + what); };
+    Step s;
+    if (int rc = step_setup(me, true, qkv, ld, dout, lddo, {table, r_in, a_in, work, a_out}, base, r_out, B, T, H, W, heads,
+                            head_dim, wt, wh, ww, st, sh, sw, full_t, full_h, full_w, work_elems, s))
+        return rc;
+    const int64_t ntok = s.ntok;
     const float* ins[3] = {r_in, a_in, base};
     float* outs[2] = {a_out, r_out};
     for (float* o : outs) {
         if (!o) continue;
         for (const float* i : ins)
-            if (i && overlap(o, ntok, i, ntok)) return bad(VC_ERR_INVALID_ARG, "a_out / r_out must not alias r_in, a_in or base");
-        if (overlap(work, work_elems, o, ntok)) return bad(VC_ERR_INVALID_ARG, "work must not alias an input or an output");
+            if (i && overlap(o, ntok, i, ntok)) return bad("a_out / r_out must not alias r_in, a_in or base");
+        if (overlap(work, work_elems, o, ntok)) return bad("work must not alias an input or an output");
     }
     for (const float* i : ins)
-        if (i && overlap(work, work_elems, i, ntok)) return bad(VC_ERR_INVALID_ARG, "work must not alias an input or an output");
-    if (r_out && overlap(a_out, ntok, r_out, ntok)) return bad(VC_ERR_INVALID_ARG, "a_out must not alias r_out");
-    static bool attr_set = false;  // benign race (idempotent)
-    if (glds > 64 * 1024 && !attr_set) {
-        hipError_t e = hipFuncSetAttribute((const void*)window_grad_rollout_cols_kernel,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)GLDS_MAX);
-        if (e != hipSuccess) return fail((int)e, std::string(me) + ": hipFuncSetAttribute: " + hipGetErrorString(e));
-        attr_set = true;
-    }
-    const WinGeom g{(int)T, (int)H, (int)W, wt, wh, ww, st, sh, sw, (int)(T / wt), (int)(H / wh), (int)(W / ww)};
-    const FullWin fw{full_t, full_h, full_w};
-    float* mbuf = work + heads * ntok;
-    float* wbuf = work + 2 * heads * ntok;
-    window_rollout_norm_kernel<<<(unsigned)nblk, NT, (size_t)lds, stream>>>(qkv, ld, g, fw, (int)heads, vol, NP, table,
-                                                                           (int)ntab, r_in, ntok, mbuf, wbuf);
-    int rc = check_launch(me);
-    if (rc) return rc;
-    window_grad_rollout_cols_kernel<<<(unsigned)nblk, NT, (size_t)glds, stream>>>(
-        qkv, ld, dout, lddo, g, fw, (int)heads, vol, NP, table, (int)ntab, mbuf, wbuf, ntok, work);
-    rc = check_launch(me);
-    if (rc) return rc;
-    window_grad_rollout_finish<<<(unsigned)((ntok + 255) / 256), 256, 0, stream>>>(work, a_in, base, ntok, (int)heads,
-                                                                                  alpha, beta, a_out, r_out);
-    return check_launch(me);
+        if (i && overlap(work, work_elems, i, ntok)) return bad("work must not alias an input or an output");
+    if (r_out && overlap(a_out, ntok, r_out, ntok)) return bad("a_out must not alias r_out");
+    return step_launch(me, s, qkv, ld, dout, lddo, table, r_in, a_in, base, (int)heads, alpha, beta, work, a_out, r_out,
+                       stream);
 }
 
 extern "C" int vc_merge_rollout_spread(const float* r_parent, int64_t B, int64_t T, int64_t H, int64_t W, float* r_child,

@@ -15,7 +15,7 @@ from __future__ import annotations
 
 import torch
 
-from . import ops
+from . import explaining, ops
 
 MODES = ("deletion", "insertion")
 BASELINES = ("zero", "blur")
@@ -83,8 +83,7 @@ def _family(model):
 
 
 def _host_map(saliency, B: int, thw) -> torch.Tensor:
-    from .vivit import Explanation
-    sal = saliency.saliency if isinstance(saliency, Explanation) else saliency
+    sal = saliency.saliency if isinstance(saliency, explaining.Explanation) else saliency
     if not isinstance(sal, torch.Tensor):
         raise ValueError("saliency must be an Explanation of a dense batch or a [B, Tg, Hg, Wg] tensor")
     if sal.dim() != 4 or sal.shape[0] != B:
@@ -100,13 +99,7 @@ def _host_map(saliency, B: int, thw) -> torch.Tensor:
 
 
 def _targets(target, B: int, labels: int):
-    from .vivit import VivitForVideoClassification
-    target, scalar = VivitForVideoClassification._check_targets(target, max(labels, 2))
-    if target is not None:
-        target = target * B if scalar else target
-        if len(target) != B:
-            raise ValueError(f"target has {len(target)} entries for {B} clips")
-    return target
+    return explaining.expand_targets(*explaining.check_targets(target, max(labels, 2)), B, who="")
 
 
 def _score(logits: torch.Tensor, target: list, labels: int) -> torch.Tensor:

@@ -5,7 +5,8 @@ weights version and the "is the cached pack still valid" check (all five familie
 FusedVideoModel: what the four fused inference models (ViViT, TimeSformer, Swin3D, ResNet3D) add to it: the
 workspace cache, the batch split over HIP streams (vclip_amd.streams.run_split) and graph replay
 (streams.GraphReplay).  A family provides _check_input, _pack, _workspace and _forward_part, and may
-override _graph_knobs, _graph_keep, _clean_state_dict.
+override _graph_knobs, _graph_keep, _clean_state_dict.  The explain paths' shared part is
+vclip_amd.explaining.
 """
 from __future__ import annotations
 
@@ -15,6 +16,7 @@ import numpy as np
 import torch
 
 from . import streams
+from .explaining import cached_explain
 
 
 def round_up(x, m):
@@ -118,6 +120,10 @@ class FusedVideoModel(ParamStore):
         if not any(w is ws for w in self._ws_used):
             self._ws_used.append(ws)
         return ws
+
+    # explain's buffers (self._explain_ws, or a cache of the family's own): cache[key], built on first use, the cache
+    # emptied first when it holds `limit` entries
+    _cached_explain = staticmethod(cached_explain)
 
     # ---- the family's part ------------------------------------------------------------------
     def _check_input(self, x):

@@ -949,20 +949,27 @@ def attention_rollout_work(B: int, S: int, H: int, device) -> torch.Tensor:
     return torch.zeros(B * H * S, dtype=torch.float32, device=device)
 
 
+def _check_attention_rollout(name, qkv, dout, lse, r_in, B, S, H, work, r_out):
+    """what attention_rollout_step and attention_grad_rollout_step (dout given) ask of their tensors"""
+    _dev(*(t for t in (qkv, dout, lse, r_in, work, r_out) if t is not None))
+    _need(lse.dtype == torch.float32 and lse.is_contiguous() and lse.numel() >= B * H * S, "lse: f32 [B*H*S]")
+    _need(qkv.dtype == torch.bfloat16 and qkv.dim() == 2 and qkv.stride(1) == 1, f"{name}: qkv bf16 rows")
+    _need(qkv.shape[1] >= 3 * H * 64 and qkv.shape[0] >= B * S, f"{name}: qkv rows / columns")
+    if dout is not None:
+        _need(dout.dtype == torch.bfloat16 and dout.dim() == 2 and dout.stride(1) == 1, f"{name}: dout bf16 rows")
+        _need(dout.shape[1] >= H * 64 and dout.shape[0] >= B * S, f"{name}: dout rows / columns")
+    for t, nm in ((r_in, "r_in"), (r_out, "r_out")):
+        _need(t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (B, S), f"{name}: {nm} f32 [B, S]")
+    _need(work.dtype == torch.float32 and work.is_contiguous() and work.numel() >= B * H * S,
+          f"{name} work: contiguous f32 [B*H*S]")
+
+
 def attention_rollout_step(qkv: torch.Tensor, lse: torch.Tensor, r_in: torch.Tensor, B: int, S: int, H: int,
                            alpha: float, work: torch.Tensor, r_out: torch.Tensor) -> torch.Tensor:
     """One attention-rollout step of the CLS row (vc_attention_rollout_step): r_out = alpha * mean_h(P_h^T r_in)
     + (1 - alpha) * r_in with P_h recomputed from qkv bf16 [>= B*S, >= 3*H*64] (q pre-scaled) and the lse f32
     [B*H*S] of attention_fwd_lse.  r_in / r_out f32 [B, S]; work from attention_rollout_work."""
-    _dev(qkv, lse, r_in, work, r_out)
-    _need(lse.dtype == torch.float32 and lse.is_contiguous() and lse.numel() >= B * H * S, "lse: f32 [B*H*S]")
-    _need(qkv.dtype == torch.bfloat16 and qkv.dim() == 2 and qkv.stride(1) == 1, "attention_rollout_step: qkv bf16 rows")
-    _need(qkv.shape[1] >= 3 * H * 64 and qkv.shape[0] >= B * S, "attention_rollout_step: qkv rows / columns")
-    for t, nm in ((r_in, "r_in"), (r_out, "r_out")):
-        _need(t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (B, S),
-              f"attention_rollout_step: {nm} f32 [B, S]")
-    _need(work.dtype == torch.float32 and work.is_contiguous() and work.numel() >= B * H * S,
-          "attention_rollout_step work: contiguous f32 [B*H*S]")
+    _check_attention_rollout("attention_rollout_step", qkv, None, lse, r_in, B, S, H, work, r_out)
     _lib.call("vc_attention_rollout_step", _p(qkv), qkv.stride(0), _p(lse), _p(r_in), B, S, H, 64, float(alpha),
               _p(work), work.numel(), _p(r_out), _stream(qkv))
     return r_out
@@ -975,19 +982,8 @@ def attention_grad_rollout_step(qkv: torch.Tensor, dout: torch.Tensor, lse: torc
     mean_h(max(P_h * dP_h, 0)^T r_in) + beta * r_in, P_h as attention_rollout_step's and dP_h[i][j] = dout_h[i] . v_j
     with dout bf16 [>= B*S, >= H*64] (head h at columns 64h, attention_bwd's `dout`).  work from
     attention_rollout_work."""
-    _dev(qkv, dout, lse, r_in, work, r_out)
-    _need(lse.dtype == torch.float32 and lse.is_contiguous() and lse.numel() >= B * H * S, "lse: f32 [B*H*S]")
-    _need(qkv.dtype == torch.bfloat16 and qkv.dim() == 2 and qkv.stride(1) == 1,
-          "attention_grad_rollout_step: qkv bf16 rows")
-    _need(qkv.shape[1] >= 3 * H * 64 and qkv.shape[0] >= B * S, "attention_grad_rollout_step: qkv rows / columns")
-    _need(dout.dtype == torch.bfloat16 and dout.dim() == 2 and dout.stride(1) == 1,
-          "attention_grad_rollout_step: dout bf16 rows")
-    _need(dout.shape[1] >= H * 64 and dout.shape[0] >= B * S, "attention_grad_rollout_step: dout rows / columns")
-    for t, nm in ((r_in, "r_in"), (r_out, "r_out")):
-        _need(t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (B, S),
-              f"attention_grad_rollout_step: {nm} f32 [B, S]")
-    _need(work.dtype == torch.float32 and work.is_contiguous() and work.numel() >= B * H * S,
-          "attention_grad_rollout_step work: contiguous f32 [B*H*S]")
+    _dev(dout)
+    _check_attention_rollout("attention_grad_rollout_step", qkv, dout, lse, r_in, B, S, H, work, r_out)
     _lib.call("vc_attention_grad_rollout_step", _p(qkv), qkv.stride(0), _p(dout), dout.stride(0), _p(lse), _p(r_in), B,
               S, H, 64, float(alpha), float(beta), _p(work), work.numel(), _p(r_out), _stream(qkv))
     return r_out
@@ -1021,6 +1017,30 @@ def window_rollout_work(B: int, grid, heads: int, device) -> torch.Tensor:
     return torch.zeros(3 * heads * B * T * H * W, dtype=torch.float32, device=device)
 
 
+def _check_window_rollout(name, qkv, table, B, grid, heads, window, full_window, work, vectors, dout=None):
+    """what window_rollout_step and window_grad_rollout_step (dout given) ask of their tensors; vectors: (f32
+    [B*T*H*W] tensor or None, its name) pairs"""
+    T, H, W = grid
+    wt, wh, ww = window
+    ft, fh, fw = full_window
+    ntok = B * T * H * W
+    ntab = (2 * ft - 1) * (2 * fh - 1) * (2 * fw - 1)
+    _dev(*(t for t in (qkv, dout, table, work, *(v for v, _ in vectors)) if t is not None))
+    _need(qkv.dtype == torch.bfloat16 and qkv.dim() == 2 and qkv.stride(1) == 1, f"{name}: qkv bf16 rows")
+    _need(qkv.shape[1] >= 3 * heads * 32 and qkv.shape[0] >= ntok, f"{name}: qkv rows / columns")
+    if dout is not None:
+        _need(dout.dtype == torch.bfloat16 and dout.dim() == 2 and dout.stride(1) == 1, f"{name}: dout bf16 rows")
+        _need(dout.shape[1] >= heads * 32 and dout.shape[0] >= ntok, f"{name}: dout rows / columns")
+    _need(table.dtype == torch.float32 and table.is_contiguous() and tuple(table.shape) == (ntab, heads),
+          f"{name} table: f32 [ntab, heads]")
+    for t, nm in vectors:
+        _need(t is None or (t.dtype == torch.float32 and t.is_contiguous() and t.numel() == ntok),
+              f"{name}: {nm} f32 [B*T*H*W]")
+    _need(T % wt == 0 and H % wh == 0 and W % ww == 0, f"{name}: grid must be whole windows")
+    _need(work.dtype == torch.float32 and work.is_contiguous() and work.numel() >= 3 * heads * ntok,
+          f"{name} work: contiguous f32 [3*heads*B*T*H*W]")
+
+
 def window_rollout_step(qkv: torch.Tensor, table: torch.Tensor, r_in: torch.Tensor, B: int, grid, heads: int, window,
                         shift, full_window, alpha: float, work: torch.Tensor, r_out: torch.Tensor) -> torch.Tensor:
     """One block step of attention rollout through Swin's shifted-window attention (vc_window_rollout_step): r_out[j]
@@ -1028,23 +1048,10 @@ def window_rollout_step(qkv: torch.Tensor, table: torch.Tensor, r_in: torch.Tens
     qkv bf16 [>= B*T*H*W, >= 3*heads*32] (q pre-scaled; v is not read) and its bias table f32 [ntab, heads] of the full
     window, with the shift-region mask.  window / shift: the effective ones (swin3d.window_and_shift).  r_in / r_out
     f32 [B*T*H*W] (any shape of that many elements); work from window_rollout_work."""
-    _dev(qkv, table, r_in, work, r_out)
-    T, H, W = grid
-    wt, wh, ww = window
-    st, sh, sw = shift
-    ft, fh, fw = full_window
-    ntok = B * T * H * W
-    ntab = (2 * ft - 1) * (2 * fh - 1) * (2 * fw - 1)
-    _need(qkv.dtype == torch.bfloat16 and qkv.dim() == 2 and qkv.stride(1) == 1, "window_rollout_step: qkv bf16 rows")
-    _need(qkv.shape[1] >= 3 * heads * 32 and qkv.shape[0] >= ntok, "window_rollout_step: qkv rows / columns")
-    _need(table.dtype == torch.float32 and table.is_contiguous() and tuple(table.shape) == (ntab, heads),
-          "window_rollout_step table: f32 [ntab, heads]")
-    for t, nm in ((r_in, "r_in"), (r_out, "r_out")):
-        _need(t.dtype == torch.float32 and t.is_contiguous() and t.numel() == ntok,
-              f"window_rollout_step: {nm} f32 [B*T*H*W]")
-    _need(T % wt == 0 and H % wh == 0 and W % ww == 0, "window_rollout_step: grid must be whole windows")
-    _need(work.dtype == torch.float32 and work.is_contiguous() and work.numel() >= 3 * heads * ntok,
-          "window_rollout_step work: contiguous f32 [3*heads*B*T*H*W]")
+    _dev(r_in, r_out)
+    _check_window_rollout("window_rollout_step", qkv, table, B, grid, heads, window, full_window, work,
+                          ((r_in, "r_in"), (r_out, "r_out")))
+    (T, H, W), (wt, wh, ww), (st, sh, sw), (ft, fh, fw) = grid, window, shift, full_window
     _lib.call("vc_window_rollout_step", _p(qkv), qkv.stride(0), _p(table), _p(r_in), B, T, H, W, heads, 32, wt, wh, ww,
               st, sh, sw, ft, fh, fw, float(alpha), _p(work), work.numel(), _p(r_out), _stream(qkv))
     return r_out
@@ -1065,29 +1072,11 @@ def window_grad_rollout_step(qkv: torch.Tensor, dout: torch.Tensor, table: torch
     base.  qkv / table / window / shift / full_window as window_rollout_step takes them (v is read here); dout bf16
     [>= B*T*H*W, >= heads*32] rows of dL/dO with any leading dimension that is a multiple of 8.  r_in / a_in / base /
     a_out / r_out f32 [B*T*H*W]; the outputs alias no input; work from window_grad_rollout_work."""
-    _dev(qkv, dout, table, r_in, a_in, work, a_out)
-    T, H, W = grid
-    wt, wh, ww = window
-    st, sh, sw = shift
-    ft, fh, fw = full_window
-    ntok = B * T * H * W
-    ntab = (2 * ft - 1) * (2 * fh - 1) * (2 * fw - 1)
-    nm_ = "window_grad_rollout_step"
-    _need(qkv.dtype == torch.bfloat16 and qkv.dim() == 2 and qkv.stride(1) == 1, f"{nm_}: qkv bf16 rows")
-    _need(qkv.shape[1] >= 3 * heads * 32 and qkv.shape[0] >= ntok, f"{nm_}: qkv rows / columns")
-    _need(dout.dtype == torch.bfloat16 and dout.dim() == 2 and dout.stride(1) == 1, f"{nm_}: dout bf16 rows")
-    _need(dout.shape[1] >= heads * 32 and dout.shape[0] >= ntok, f"{nm_}: dout rows / columns")
-    _need(table.dtype == torch.float32 and table.is_contiguous() and tuple(table.shape) == (ntab, heads),
-          f"{nm_} table: f32 [ntab, heads]")
-    _need((base is None) == (r_out is None), f"{nm_}: base and r_out come together")
-    for t, nm in ((r_in, "r_in"), (a_in, "a_in"), (a_out, "a_out"), (base, "base"), (r_out, "r_out")):
-        if t is None:
-            continue
-        _dev(qkv, t)
-        _need(t.dtype == torch.float32 and t.is_contiguous() and t.numel() == ntok, f"{nm_}: {nm} f32 [B*T*H*W]")
-    _need(T % wt == 0 and H % wh == 0 and W % ww == 0, f"{nm_}: grid must be whole windows")
-    _need(work.dtype == torch.float32 and work.is_contiguous() and work.numel() >= 3 * heads * ntok,
-          f"{nm_} work: contiguous f32 [3*heads*B*T*H*W]")
+    _dev(dout, r_in, a_in, a_out)
+    _need((base is None) == (r_out is None), "window_grad_rollout_step: base and r_out come together")
+    _check_window_rollout("window_grad_rollout_step", qkv, table, B, grid, heads, window, full_window, work,
+                          ((r_in, "r_in"), (a_in, "a_in"), (a_out, "a_out"), (base, "base"), (r_out, "r_out")), dout=dout)
+    (T, H, W), (wt, wh, ww), (st, sh, sw), (ft, fh, fw) = grid, window, shift, full_window
     _lib.call("vc_window_grad_rollout_step", _p(qkv), qkv.stride(0), _p(dout), dout.stride(0), _p(table), _p(r_in), _p(a_in),
               None if base is None else _p(base), B, T, H, W, heads, 32, wt, wh, ww, st, sh, sw, ft, fh, fw, float(alpha),
               float(beta), _p(work), work.numel(), _p(a_out), None if r_out is None else _p(r_out), _stream(qkv))

@@ -18,7 +18,8 @@ from __future__ import annotations
 
 import torch
 
-from . import ops
+from . import explaining, ops
+from .explaining import Explanation
 from .hosting import FusedVideoModel, round_up as _ru
 from .weights import resnet3d_param_shapes
 
@@ -437,11 +438,10 @@ class ResNet3d(FusedVideoModel):
         layer, device).  Per block after the layer: its a / b / output, its masked output gradient `d`, and the two
         gradients its input receives (dIn, and dsk when the skip is a convolution); the GEMM and col2im outputs
         consumed at once are shared scratch, sized by the largest block."""
-        key = (B, T, H, W, layer, str(device))
-        if key in self._explain_ws:
-            return self._explain_ws[key]
-        if len(self._explain_ws) >= 2:
-            self._explain_ws = {}
+        return self._cached_explain(self._explain_ws, (B, T, H, W, layer, str(device)),
+                                    lambda: self._build_explain_buffers(B, T, H, W, layer, device))
+
+    def _build_explain_buffers(self, B, T, H, W, layer, device):
         c, pk = self.cfg, self._packed
         n = len(c["depths"])
         ls = n - 1 if layer == "res5" else n - 2
@@ -497,7 +497,6 @@ class ResNet3d(FusedVideoModel):
         if buf["chain"]:
             buf["g"] = z(rows(gl), Cl)
         buf["kept_bytes"] = buf["x"].numel() * 2 + sum(t.numel() * 2 for kb in buf["blocks"].values() for t in kb.values())
-        self._explain_ws[key] = buf
         return buf
 
     def _explain_chain(self, buf, B: int) -> torch.Tensor:
@@ -591,24 +590,15 @@ class ResNet3d(FusedVideoModel):
         and logits buffer are untouched.  Refuses (no fallback): training mode, CPU tensors, an unknown method or
         layer ("res2" / "res3" are not supported), a bad target, a video that is not [B, 3, T, H, W], a head pool
         that does not fit the final grid."""
-        from .vivit import Explanation, VivitForVideoClassification
         c = self.cfg
-        if method not in self.EXPLAIN_METHODS:
-            raise ValueError(f"explain: method must be one of {self.EXPLAIN_METHODS}, not {method!r}")
+        explaining.require_method(method, self.EXPLAIN_METHODS)
         if layer not in self.EXPLAIN_LAYERS:
             raise ValueError(f"explain: layer must be one of {self.EXPLAIN_LAYERS}, not {layer!r}")
-        if self.training:
-            raise RuntimeError("explain: inference only; call model.eval() first")
-        if not isinstance(video, torch.Tensor) or video.device.type != "cuda":
-            raise RuntimeError("explain runs on the GPU only: move the clip batch to cuda")
+        explaining.require_explainable(self, video)
         if video.dim() != 5 or video.shape[1] != 3:
             raise ValueError(f"video {tuple(video.shape)} must be [B, 3, T, H, W]")
         B, _, T, H, W = video.shape
-        target, scalar = VivitForVideoClassification._check_targets(target, c["num_classes"])
-        if target is not None:
-            target = target * B if scalar else target
-            if len(target) != B:
-                raise ValueError(f"explain: target has {len(target)} entries for {B} clips")
+        target = explaining.expand_targets(*explaining.check_targets(target, c["num_classes"]), B)
         _, grids = self.geometry(T, H, W)
         gf = grids[-1]
         if any(k <= 0 or k > n for k, n in zip(c["head_pool"], gf)):
@@ -638,9 +628,7 @@ class ResNet3d(FusedVideoModel):
             tm("cam_map_kernel<true>", "cam.map", B * Nl * Cl * 4, "byte", ops.cam_map, "hirescam", buf["x"], G, B, Nl, Cl,
                buf["map"])
         rel = buf["map"].cpu().reshape(B, Nl)  # the one copy; the rest is host bookkeeping
-        pos = rel.double().clamp_min(0)
-        tot = pos.sum(dim=1, keepdim=True)
-        sal = torch.where(tot > 0, pos / tot.clamp_min(1e-300), torch.zeros_like(pos)).float().reshape(B, Tl, Hl, Wl)
+        sal = explaining.normalise(rel.double().clamp_min(0), zero_ok=True).reshape(B, Tl, Hl, Wl)
         return Explanation(logits, rel, sal.contiguous(), sal.sum(dim=(2, 3)), method, target=target)
 
 

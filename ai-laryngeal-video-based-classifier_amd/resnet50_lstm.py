@@ -43,7 +43,8 @@ import numpy as np
 import torch
 
 from . import autograd_ops as A
-from . import ops
+from . import explaining, ops
+from .explaining import Explanation
 from .hosting import ParamStore, round_up as _ru
 from .resnet3d import ResNet3d
 from .weights import RESNET50_2D, blocks_to_torchvision_resnet50, resnet50_lstm_param_shapes, \
@@ -83,6 +84,7 @@ class VideoResNet50LSTM(ParamStore):
         self._all_names = list(shapes.keys())
         self._init_params({n: s for n, s in shapes.items() if not n.startswith("resnet50.")})
         self._ws = {}
+        self._explain_ws = {}  # explain's workspace, one key at a time (_explain_workspace)
         # the last forward's bf16 feature matrix [B*T, 2048] and dropout masks ({"lstm": [per layer or None],
         # "head": mask or None}), for tests that replay them through an oracle
         self.last_features = None
@@ -450,22 +452,19 @@ class VideoResNet50LSTM(ParamStore):
     def _explain_workspace(self, rows, nseq, Pl, Cl, device):
         """explain's own buffers for `rows` frame rows in nseq sequences and a map of Pl positions x Cl channels per
         frame; one key at a time, like _workspace (which it never touches)."""
-        key = (rows, nseq, Pl, Cl, str(device))
-        ws = getattr(self, "_explain_ws", None)
-        if ws is not None and ws["key"] == key:
-            return ws
-        H, M = self.hidden, _ru(rows, 256)
-        Np, Hp = _ru(4 * H, 128), _ru(H, 128)
-        f32, bf = torch.float32, torch.bfloat16
-        z = lambda r, c, dt=f32: torch.zeros(r, c, dtype=dt, device=device)  # noqa: E731
-        ws = dict(key=key, feat=z(M, 2048, bf), pre=z(M, Np), h_prev=z(M, Hp, bf), dpre=z(rows, 4 * H), dpb=z(M, Np, bf),
-                  hseq=[z(M, Hp, bf) for _ in range(2)], gates=[z(rows, 4 * H) for _ in range(self.layers)],
-                  c_seq=[z(rows, H) for _ in range(self.layers)], h_n=z(self.layers * nseq, H).view(self.layers, nseq, H), c_n=z(self.layers * nseq, H).view(self.layers, nseq, H),
-                  dxh=z(M, Hp), g=z(M, 2048), frame_rel=z(1, rows)[0], frame_map=z(1, rows)[0], map=z(1, rows * Pl)[0],
-                  map_rel=z(1, rows)[0], alpha=z(rows, Cl), cam_work=ops.cam_weights_work(rows, Cl, device),
-                  head=self._head_buffers(nseq, device))
-        self._explain_ws = ws
-        return ws
+        def build():
+            H, M = self.hidden, _ru(rows, 256)
+            Np, Hp = _ru(4 * H, 128), _ru(H, 128)
+            f32, bf = torch.float32, torch.bfloat16
+            z = lambda r, c, dt=f32: torch.zeros(r, c, dtype=dt, device=device)  # noqa: E731
+            return dict(feat=z(M, 2048, bf), pre=z(M, Np), h_prev=z(M, Hp, bf), dpre=z(rows, 4 * H), dpb=z(M, Np, bf),
+                        hseq=[z(M, Hp, bf) for _ in range(2)], gates=[z(rows, 4 * H) for _ in range(self.layers)],
+                        c_seq=[z(rows, H) for _ in range(self.layers)], h_n=z(self.layers * nseq, H).view(self.layers, nseq, H), c_n=z(self.layers * nseq, H).view(self.layers, nseq, H),
+                        dxh=z(M, Hp), g=z(M, 2048), frame_rel=z(1, rows)[0], frame_map=z(1, rows)[0], map=z(1, rows * Pl)[0],
+                        map_rel=z(1, rows)[0], alpha=z(rows, Cl), cam_work=ops.cam_weights_work(rows, Cl, device),
+                        head=self._head_buffers(nseq, device))
+
+        return explaining.cached_explain(self._explain_ws, (rows, nseq, Pl, Cl, str(device)), build, limit=1)
 
     def _head_buffers(self, B, device):
         z = lambda *s: torch.zeros(*s, dtype=torch.float32, device=device)  # noqa: E731
@@ -493,13 +492,7 @@ class VideoResNet50LSTM(ParamStore):
 
     @staticmethod
     def _explain_targets(target, B):
-        from .vivit import VivitForVideoClassification
-        target, scalar = VivitForVideoClassification._check_targets(target, 2)
-        if target is not None:
-            target = target * B if scalar else target
-            if len(target) != B:
-                raise ValueError(f"explain: target has {len(target)} entries for {B} videos")
-        return target
+        return explaining.expand_targets(*explaining.check_targets(target, 2), B, what="videos")
 
     @staticmethod
     def _positive_share(rel: torch.Tensor) -> torch.Tensor:
@@ -546,15 +539,10 @@ class VideoResNet50LSTM(ParamStore):
         and packed weights are untouched.  Refuses (no fallback): training mode, CPU tensors, an unknown method or
         layer ("res2" / "res3" are not supported), a target outside {0, 1} or of the wrong length, a video that is
         not [B, 3, T, H, W] (ragged: [1, 3, N, H, W] with lengths >= 1 that sum to N)."""
-        from .vivit import Explanation
-        if method not in self.EXPLAIN_METHODS:
-            raise ValueError(f"explain: method must be one of {self.EXPLAIN_METHODS}, not {method!r}")
+        explaining.require_method(method, self.EXPLAIN_METHODS)
         if layer not in self.EXPLAIN_LAYERS:
             raise ValueError(f"explain: layer must be one of {self.EXPLAIN_LAYERS}, not {layer!r}")
-        if self.training:
-            raise RuntimeError("explain: inference only; call model.eval() first")
-        if not isinstance(video, torch.Tensor) or video.device.type != "cuda":
-            raise RuntimeError("explain runs on the GPU only: move the clip batch to cuda")
+        explaining.require_explainable(self, video)
         if lengths is None:
             if video.dim() != 5 or video.shape[1] != 3 or video.shape[0] < 1 or video.shape[2] < 1:
                 raise ValueError(f"video {tuple(video.shape)} must be [B, 3, T, H, W]")
@@ -735,7 +723,6 @@ class ExplainSession:
 
     @torch.no_grad()
     def finish(self, target=None):
-        from .vivit import Explanation
         m = self.model
         if self.done:
             raise RuntimeError("explain session: finish() was already called")

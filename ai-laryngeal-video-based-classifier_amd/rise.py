@@ -28,7 +28,7 @@ import torch
 
 from . import ops
 from .faithfulness import BASELINES, BLUR_KSIZE, BLUR_SIGMA, _family, _score, _targets
-from .vivit import Explanation
+from .explaining import Explanation
 
 # masks per rise_apply launch and clips per forward when rise_map's `chunk` is None, per family.  The rule is the
 # project's for the LSTM's --videos_per_batch: the smallest value whose masks/s is within 5 % of the best of the sweep

@@ -26,7 +26,8 @@ import math
 
 import torch
 
-from . import ops
+from . import explaining, ops
+from .explaining import Explanation
 from .hosting import FusedVideoModel, round_up as _ru
 from .weights import swin3d_param_shapes
 
@@ -488,10 +489,7 @@ class Swin3d(FusedVideoModel):
                  for i in range(c["depths"][s])] for s, g in enumerate(grids)]
 
     def _explain_buffers(self, B, grids, device):
-        key = (B, tuple(grids), str(device))
-        if key not in self._explain_ws:
-            if len(self._explain_ws) >= 2:
-                self._explain_ws = {}
+        def build():
             c = self.cfg
             f = lambda n: torch.zeros(n, dtype=torch.float32, device=device)  # noqa: E731
             qkv, r, work = [], [], []
@@ -504,9 +502,10 @@ class Swin3d(FusedVideoModel):
             t, h, w = grids[-1]
             # the head is W . mean_n LN(x_n): the uniform row over the last stage's tokens, made on the host
             seed = torch.full((B * t * h * w,), 1.0 / (t * h * w), dtype=torch.float32).to(device)
-            self._explain_ws[key] = dict(QKV=qkv, r=r, work=work, seed=seed,
-                                         logits=torch.zeros((B, self.num_classes), dtype=torch.float32, device=device))
-        return self._explain_ws[key]
+            return dict(QKV=qkv, r=r, work=work, seed=seed,
+                        logits=torch.zeros((B, self.num_classes), dtype=torch.float32, device=device))
+
+        return self._cached_explain(self._explain_ws, (B, tuple(grids), str(device)), build)
 
     @torch.no_grad()
     def explain(self, video: torch.Tensor, method: str = "rollout", residual: float = 0.5):
@@ -531,16 +530,10 @@ class Swin3d(FusedVideoModel):
         copied to the host once; normalisation and the sums happen there.  Refuses (no fallback): training mode,
         CPU tensors, an unknown method, residual outside (0, 1], a video that is not [B, 3, T, H, W] with T/H/W
         multiples of the patch size, stage grids that are not whole windows (which the window attention refuses)."""
-        from .vivit import Explanation
         c = self.cfg
-        if method not in self.EXPLAIN_METHODS:
-            raise ValueError(f"explain: method must be one of {self.EXPLAIN_METHODS}, not {method!r}")
-        if not 0.0 < float(residual) <= 1.0:
-            raise ValueError(f"explain: residual must be in (0, 1], not {residual}")
-        if self.training:
-            raise RuntimeError("explain: inference only; call model.eval() first")
-        if video is None or video.device.type != "cuda":
-            raise RuntimeError("explain runs on the GPU only: move the clip batch to cuda")
+        explaining.require_method(method, self.EXPLAIN_METHODS)
+        explaining.require_residual(residual)
+        explaining.require_explainable(self, video)
         if video.dim() != 5 or video.shape[1] != 3:
             raise ValueError(f"video {tuple(video.shape)} must be [B, 3, T, H, W]")
         B, _, T, H, W = video.shape
@@ -568,17 +561,13 @@ class Swin3d(FusedVideoModel):
                 r_in = ops.merge_rollout_spread(r_in, B, grids[s - 1], buf["r"][s - 1][0])
         t0, h0, w0 = grids[0]
         rel = r_in.cpu().reshape(B, t0 * h0 * w0)  # the one copy; the rest is host bookkeeping
-        rd = rel.double()
-        sal = (rd / rd.sum(dim=1, keepdim=True)).float().reshape(B, t0, h0, w0).contiguous()
+        sal = explaining.normalise(rel.double(), zero_ok=False).reshape(B, t0, h0, w0).contiguous()
         return Explanation(logits, rel, sal, sal.sum(dim=(2, 3)), method)
 
     def _explain_class_buffers(self, B, grids, device):
         """explain_class's rollout vectors per (B, geometry, device): per stage the two a and the two r buffers, the
         step's scratch and `base`, the uniform seed carried through the hops alone (geometry only, made once)"""
-        key = (B, tuple(grids), str(device))
-        if key not in self._explain_class_ws:
-            if len(self._explain_class_ws) >= 2:
-                self._explain_class_ws = {}
+        def build():
             c = self.cfg
             f = lambda n: torch.zeros(n, dtype=torch.float32, device=device)  # noqa: E731
             a, r, work, base = [], [], [], [None] * len(grids)
@@ -592,8 +581,9 @@ class Swin3d(FusedVideoModel):
             for s in reversed(range(len(grids) - 1)):
                 t, h, w = grids[s]
                 base[s] = ops.merge_rollout_spread(base[s + 1], B, grids[s], f(B * t * h * w))
-            self._explain_class_ws[key] = dict(a=a, r=r, work=work, base=base)
-        return self._explain_class_ws[key]
+            return dict(a=a, r=r, work=work, base=base)
+
+        return self._cached_explain(self._explain_class_ws, (B, tuple(grids), str(device)), build)
 
     def explain_class(self, video: torch.Tensor, target=None):
         """The logits and which part of the clip speaks for ONE class: the gradient-weighted rollout of Chefer, Gur &
@@ -621,22 +611,12 @@ class Swin3d(FusedVideoModel):
         and packed weights are untouched.  Refuses (no fallback): training mode, CPU tensors, a video that is not
         [B, 3, T, H, W] with T/H/W multiples of the patch size, stage grids that are not whole windows, a target
         outside [0, classes) or not B of them."""
-        from .vivit import Explanation, VivitForVideoClassification
-        try:
-            target, scalar = VivitForVideoClassification._check_targets(target, self.num_classes)
-        except ValueError as e:  # the shared check names ViViT's method
-            raise ValueError(str(e).replace("explain:", "explain_class:", 1)) from None
-        if self.training:
-            raise RuntimeError("explain_class: inference only; call model.eval() first")
-        if video is None or video.device.type != "cuda":
-            raise RuntimeError("explain_class runs on the GPU only: move the clip batch to cuda")
+        target, scalar = explaining.check_targets(target, self.num_classes, who="explain_class")
+        explaining.require_explainable(self, video, who="explain_class")
         if video.dim() != 5 or video.shape[1] != 3:
             raise ValueError(f"video {tuple(video.shape)} must be [B, 3, T, H, W]")
         B, _, T, H, W = video.shape
-        if target is not None:
-            target = target * B if scalar else target
-            if len(target) != B:
-                raise ValueError(f"explain_class: target has {len(target)} entries for {B} clips")
+        target = explaining.expand_targets(target, scalar, B, who="explain_class")
         grids = self.geometry(B, T, H, W)  # ValueError unless T/H/W are multiples of the patch size
         wins = self._block_windows(grids)
         for s, g in enumerate(grids):
@@ -653,10 +633,7 @@ class Swin3d(FusedVideoModel):
             a = self._class_rollout(buf, pk, kept, douts, B, grids, wins)
             t0, h0, w0 = grids[0]
             rel = a.cpu().reshape(B, t0 * h0 * w0)  # the one copy; the rest is host bookkeeping
-        rd = rel.double()
-        total = rd.sum(dim=1, keepdim=True)
-        sal = torch.where(total > 0, rd / torch.where(total > 0, total, torch.ones_like(total)), torch.zeros_like(rd))
-        sal = sal.float().reshape(B, t0, h0, w0).contiguous()
+        sal = explaining.normalise(rel.double(), zero_ok=True).reshape(B, t0, h0, w0).contiguous()
         return Explanation(logits, rel, sal, sal.sum(dim=(2, 3)), "class_rollout", target=target)
 
     def _class_chain(self, x, target, frozen: bool = True):

@@ -27,7 +27,8 @@ import math
 
 import torch
 
-from . import ops
+from . import explaining, ops
+from .explaining import Explanation
 from .hosting import FusedVideoModel, round_up
 from .vivit import ClassifierOutput
 from .weights import timesformer_param_shapes
@@ -280,10 +281,7 @@ class TimesformerForVideoClassification(FusedVideoModel):
     EXPLAIN_METHODS = ("rollout", "cls_attention")
 
     def _explain_buffers(self, B, device):
-        key = (B, str(device))
-        if key not in self._explain_ws:
-            if len(self._explain_ws) >= 2:
-                self._explain_ws = {}
+        def build():
             c = self.config
             P, T, S, Mpad, _ = self.geometry(B)
             Hn, nl = c.num_attention_heads, c.num_hidden_layers
@@ -291,10 +289,11 @@ class TimesformerForVideoClassification(FusedVideoModel):
             seed[:, 0] = 1.0 / T  # e_CLS in the frame layout, made on the host: every frame's slot 0 holds r_CLS / T
             f = lambda *s: torch.zeros(s, dtype=torch.float32, device=device)  # noqa: E731
             q = lambda: torch.zeros(nl, Mpad, 3 * c.hidden_size, dtype=torch.bfloat16, device=device)  # noqa: E731
-            self._explain_ws[key] = dict(QKV_t=q(), QKV_s=q(), LSE_s=f(nl, B * T * Hn * (1 + P)), seed=seed.to(device),
-                                         r_frame=(f(B * T, 1 + P), f(B * T, 1 + P)), r_clip=f(B, S),
-                                         work=ops.attention_rollout_work(B * T, 1 + P, Hn, device))
-        return self._explain_ws[key]
+            return dict(QKV_t=q(), QKV_s=q(), LSE_s=f(nl, B * T * Hn * (1 + P)), seed=seed.to(device),
+                        r_frame=(f(B * T, 1 + P), f(B * T, 1 + P)), r_clip=f(B, S),
+                        work=ops.attention_rollout_work(B * T, 1 + P, Hn, device))
+
+        return self._cached_explain(self._explain_ws, (B, str(device)), build)
 
     @torch.no_grad()
     def explain(self, pixel_values: torch.Tensor, method: str = "rollout", residual: float = 0.5):
@@ -323,16 +322,10 @@ class TimesformerForVideoClassification(FusedVideoModel):
         and logits are untouched.  The result is copied to the host once; normalisation and the sums happen there.
         Refuses (no fallback): training mode, CPU tensors, an unknown method (the class-specific "grad_rollout" is
         ViViT's only), residual outside (0, 1], shapes that do not match the config, B*T*heads > 65535."""
-        from .vivit import Explanation
         c = self.config
-        if method not in self.EXPLAIN_METHODS:
-            raise ValueError(f"explain: method must be one of {self.EXPLAIN_METHODS}, not {method!r}")
-        if not 0.0 < float(residual) <= 1.0:
-            raise ValueError(f"explain: residual must be in (0, 1], not {residual}")
-        if self.training:
-            raise RuntimeError("explain: inference only; call model.eval() first")
-        if pixel_values is None or pixel_values.device.type != "cuda":
-            raise RuntimeError("explain runs on the GPU only: move pixel_values to cuda")
+        explaining.require_method(method, self.EXPLAIN_METHODS)
+        explaining.require_residual(residual)
+        explaining.require_explainable(self, pixel_values, what="pixel_values")
         if pixel_values.dim() != 5:
             raise ValueError(f"pixel_values {tuple(pixel_values.shape)} must be [B, T, C, H, W]")
         B, T, C, H, W = pixel_values.shape
@@ -365,7 +358,7 @@ class TimesformerForVideoClassification(FusedVideoModel):
                              r_f[:, :, 1:].transpose(1, 2).reshape(B, P * T)], dim=1).contiguous()
         g = c.image_size // c.patch_size
         patch = rel[:, 1:].double().reshape(B, P, T).transpose(1, 2)  # token (p, t) -> [t, p]
-        sal = (patch / patch.sum(dim=(1, 2), keepdim=True)).float().reshape(B, T, g, g).contiguous()
+        sal = explaining.normalise(patch, zero_ok=False).reshape(B, T, g, g).contiguous()
         return Explanation(logits, rel, sal, sal.sum(dim=(2, 3)), method)
 
     def _forward_train(self, pix: torch.Tensor) -> torch.Tensor:

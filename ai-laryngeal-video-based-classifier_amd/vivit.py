@@ -20,13 +20,12 @@ from __future__ import annotations
 import functools
 import json
 import math
-import operator
 from collections import OrderedDict
 
-import numpy as np
 import torch
 
-from . import ops
+from . import explaining, ops
+from .explaining import Explanation
 from .hosting import FusedVideoModel, round_up
 from .vivit_explain import GradRolloutEngine
 from .vivit_train import FlatLayout, TrainEngine, VivitTrainFn
@@ -75,22 +74,6 @@ class VivitConfig:
 
     def __repr__(self):
         return f"VivitConfig({json.dumps(self.to_dict())})"
-
-
-class Explanation:
-    """What VivitForVideoClassification.explain returns: `logits` f32 [B, labels] on the device;
-    `token_relevance` f32 [B, S] (column 0 is CLS), `saliency` f32 [B, T/kt, H/kh, W/kw] (the patch tokens'
-    relevance divided by its per-clip sum) and `temporal` f32 [B, T/kt] (saliency summed over space) on the host.
-    `target`: the B class indices a class-specific method ("grad_rollout"; ResNet3d.explain's Grad-CAM / HiResCAM, whose
-    `token_relevance` is the signed map with no CLS column) explained, None for the others.
-    `frame_relevance`: VideoResNet50LSTM.explain's signed gradient x input per frame, f32 [B, T] on the host (a list
-    of per-video tensors for ragged batches and streamed recordings); None for every other family."""
-
-    def __init__(self, logits, token_relevance, saliency, temporal, method, target=None, frame_relevance=None):
-        self.logits, self.token_relevance, self.saliency, self.temporal = logits, token_relevance, saliency, temporal
-        self.method = method
-        self.target = target
-        self.frame_relevance = frame_relevance
 
 
 class ClassifierOutput:
@@ -580,20 +563,18 @@ class VivitForVideoClassification(FusedVideoModel):
     EXPLAIN_METHODS = ("rollout", "cls_attention", "grad_rollout")
 
     def _explain_buffers(self, B, device):
-        key = (B, str(device))
-        if key not in self._explain_ws:
-            if len(self._explain_ws) >= 2:
-                self._explain_ws = {}
+        def build():
             c = self.config
             _, S, Mpad, _ = self.geometry(B)
             Hn, nl = c.num_attention_heads, c.num_hidden_layers
             seed = torch.zeros(B, S, dtype=torch.float32)
             seed[:, 0] = 1.0  # e_CLS, made on the host: one copy, no device arithmetic
             f = lambda *s: torch.zeros(s, dtype=torch.float32, device=device)  # noqa: E731
-            self._explain_ws[key] = dict(QKV=torch.zeros(nl, Mpad, 3 * c.hidden_size, dtype=torch.bfloat16, device=device),
-                                         LSE=f(nl, B * Hn * S), seed=seed.to(device), r=(f(B, S), f(B, S)),
-                                         work=ops.attention_rollout_work(B, S, Hn, device))
-        return self._explain_ws[key]
+            return dict(QKV=torch.zeros(nl, Mpad, 3 * c.hidden_size, dtype=torch.bfloat16, device=device),
+                        LSE=f(nl, B * Hn * S), seed=seed.to(device), r=(f(B, S), f(B, S)),
+                        work=ops.attention_rollout_work(B, S, Hn, device))
+
+        return self._cached_explain(self._explain_ws, (B, str(device)), build)
 
     def _explain_grad_engine(self, B, device):
         key = (B, str(device))
@@ -605,37 +586,19 @@ class VivitForVideoClassification(FusedVideoModel):
     def _explain_targets(self, target):
         """`target` of explain checked against the labels: (None or a list of class indices, whether it was one int
         for every clip)"""
-        return self._check_targets(target, self.config.num_labels)
+        return explaining.check_targets(target, self.config.num_labels)
 
     @staticmethod
     def _check_targets(target, nl: int):
-        """_explain_targets against `nl` labels (shared with ResNet3d.explain)"""
-        if target is None:
-            return None, False
-        if isinstance(target, torch.Tensor):
-            if target.is_floating_point() or target.dtype == torch.bool:
-                raise ValueError("explain: target must hold integers")
-            target = target.tolist()
-        if isinstance(target, bool):
-            raise ValueError("explain: target must be None, an int or a sequence of B ints")
-        scalar = not isinstance(target, (list, tuple, np.ndarray))
-        try:
-            target = [operator.index(target)] if scalar else [operator.index(t) for t in target]
-        except TypeError:
-            raise ValueError("explain: target must be None, an int or a sequence of B ints") from None
-        if any(not 0 <= t < nl for t in target):
-            raise ValueError(f"explain: target {target} out of range for {nl} labels")
-        return target, scalar
+        """explaining.check_targets against `nl` labels"""
+        return explaining.check_targets(target, nl)
 
     def _explain_grad_rollout(self, pix, target, scalar_target) -> Explanation:
         """explain(method="grad_rollout") past the argument checks: pix f32 contiguous on the GPU, target from
         _explain_targets"""
         c = self.config
         B, T, _, H, W = pix.shape
-        if target is not None:
-            target = target * B if scalar_target else target
-            if len(target) != B:
-                raise ValueError(f"explain: target has {len(target)} entries for {B} clips")
+        target = explaining.expand_targets(target, scalar_target, B)
         eng = self._explain_grad_engine(B, pix.device)
         logits = eng.forward(pix).clone()
         if target is None:
@@ -648,7 +611,7 @@ class VivitForVideoClassification(FusedVideoModel):
             raise RuntimeError(f"explain: grad_rollout found no positive gradient-weighted attention for target "
                                f"{target}: the patch relevances of clip(s) "
                                f"{[b for b in range(B) if not total[b, 0] > 0]} sum to 0")
-        sal = (patch / total).float().reshape(B, T // kt, H // kh, W // kw)
+        sal = explaining.normalise(patch, zero_ok=False).reshape(B, T // kt, H // kh, W // kw)
         return Explanation(logits, rel, sal, sal.sum(dim=(2, 3)), method="grad_rollout", target=target)
 
     @torch.no_grad()
@@ -681,17 +644,12 @@ class VivitForVideoClassification(FusedVideoModel):
         whose patch relevances sum to 0 (no positive product anywhere) raises RuntimeError.  Refuses what the
         other methods refuse, and a hidden_act that is not a tanh GELU."""
         c = self.config
-        if method not in self.EXPLAIN_METHODS:
-            raise ValueError(f"explain: method must be one of {self.EXPLAIN_METHODS}, not {method!r}")
+        explaining.require_method(method, self.EXPLAIN_METHODS)
         if target is not None and method != "grad_rollout":
             raise ValueError(f"explain: target is for method 'grad_rollout', not {method!r}")
         target, scalar_target = self._explain_targets(target)
-        if not 0.0 < float(residual) <= 1.0:
-            raise ValueError(f"explain: residual must be in (0, 1], not {residual}")
-        if self.training:
-            raise RuntimeError("explain: inference only; call model.eval() first")
-        if pixel_values is None or pixel_values.device.type != "cuda":
-            raise RuntimeError("explain runs on the GPU only: move pixel_values to cuda")
+        explaining.require_residual(residual)
+        explaining.require_explainable(self, pixel_values, what="pixel_values")
         if self.compute_dtype != torch.bfloat16:
             raise RuntimeError("explain: compute_dtype must be torch.bfloat16 (the lse-storing attention forward is bf16-only)")
         if self.precise_layers > 0:
@@ -722,8 +680,7 @@ class VivitForVideoClassification(FusedVideoModel):
             r_in = r_out
         rel = r_in.cpu()  # the one copy; the rest is host bookkeeping on [B, S]
         kt, kh, kw = c.tubelet_size
-        patch = rel[:, 1:].double()
-        sal = (patch / patch.sum(dim=1, keepdim=True)).float().reshape(B, T // kt, H // kh, W // kw)
+        sal = explaining.normalise(rel[:, 1:].double(), zero_ok=False).reshape(B, T // kt, H // kh, W // kw)
         return Explanation(logits, rel, sal, sal.sum(dim=(2, 3)), method)
 
 

@@ -404,7 +404,7 @@ def lstm(a) -> dict:
         buf = model.backbone._explain_buffers(B, T, 224, 224, layer, video.device)  # as the last explain left them
         r["explain"][f"{layer}.kept_bytes"] = buf["kept_bytes"]
     buf = model.backbone._explain_buffers(B, T, 224, 224, "res4", video.device)
-    ws, pk, H = model._explain_ws, model._packed, model.hidden
+    (ws,), pk, H = model._explain_ws.values(), model._packed, model.hidden  # the one workspace the last explain left
 
     def bptt():
         model._head_gradient(pk, ws["head"], ws["h_n"][model.layers - 1], [1] * B)
